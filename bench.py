@@ -36,8 +36,15 @@ exercised at rates comparable to a trained pair.  ``--pair random`` uses indepen
 ~0: value = 1 / step latency).  ms_per_step, bytes per step and the roofline fractions are shape-determined and do not
 depend on the pair.
 
-Extra objects on the line: ``roofline`` (dominant kernel family = the skinny weight-streaming GEMMs, timed with HIP
-events on the launch stream while rotating through all layers' weights so nothing is cache-resident; per-rank shard
+A plain run sets up, samples TTFT (the metric's p50), warms up, times ``--steps`` engine steps and prints the line: ``value``,
+``ms_per_step``, ``ttft_p50_ms``, ``mean_accepted_len`` and what follows from them arithmetically.  ``--dump-outputs DIR``
+writes what the last timed step handed its caller (the sequence's committed tokens, the suffix that step committed, its
+recovery token, and the timed steps' accepted lengths and speculation-cache hits) as float64 ``DIR/<name>.npy``; the same
+arguments give the same inputs on every run, so two builds can be compared output for output.
+
+With ``--full`` the line also carries the measurements that take runs of their own: ``ttft_first_sighting_ms``, the
+reference-protocol run (``reference_protocol``), the independent-draft floor (``random_pair``), ``roofline`` (dominant
+kernel family = the skinny weight-streaming GEMMs, timed with HIP events on the launch stream while rotating through all layers' weights so nothing is cache-resident; per-rank shard
 shapes at N > 1; where the draft's single-token forwards run as one resident launch per layer, csrc/chain.hip, that launch is
 timed as its own kind ``draft.chain_segment.M1``), ``collective`` (N > 1: which all-reduce carries the tensor-parallel sums and its measured latency)
 and ``cpu_baseline`` (the oracle engine -- the reference's own modules restated -- timed on the host cores on a
@@ -91,6 +98,11 @@ def parse(argv=None):
                     help="TTFT runs; the first two are dropped (eager first sighting of the shape, then hipGraph capture)")
     ap.add_argument("--ref-seqs", type=int, default=2, help="sequences of the reference-protocol run (512 output tokens each); 0 = skip")
     ap.add_argument("--ref-output-len", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure: first-sighting TTFT, the reference-protocol run, the "
+                         "random-pair leg, the GEMM roofline / collective probes and the CPU baseline (--no-* / --ref-seqs 0 skip single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed for its caller as DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -427,6 +439,21 @@ def cpu_baseline():
                       f"sample, ~{budget:.0f} s), bf16 weights; end-to-end wall {wall:.1f}s incl. prefill; decode-only rate reported"}
 
 
+def dump_outputs(out_dir: str, seq, lens, hits) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files (token ids are exact in float64):
+    the timed sequence's committed completion tokens, the suffix the last step committed ([recovery, accepted draft tokens...]),
+    the recovery token it computed for the next round, and the timed steps' accepted lengths and speculation-cache hits (the
+    METRICS that generate() returns).  A few kB at every workload."""
+    import numpy as np
+    assert seq is not None and lens, "--dump-outputs: the timed request finished before the last timed step"
+    comp = list(seq.completion_token_ids)
+    arrays = {"completion_token_ids": comp, "last_step_suffix": comp[len(comp) - lens[-1]:],
+              "last_step_recovery_token": [seq.recovery_token_id], "accepted_lens": lens, "cache_hits": [float(h) for h in hits]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, values in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(values, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -543,13 +570,15 @@ def run(args, guard, rank, world):
     # what a server with free-form prompt lengths sees: a shape on first sight runs eagerly (no graph yet).  Sample 0 above also
     # carries one-time costs of the process (first use of every kernel, allocator growth), so a FRESH shape is timed now that the
     # process is warm: a prompt one token shorter than any seen so far.
-    guard.stage("ttft_first_sighting")
-    first = []
-    sync_all()
-    t0 = time.perf_counter()
-    engine.generate([prompt[:-1]], SamplingParams(temperature=0, ignore_eos=True, max_new_tokens=1), use_tqdm=False,
-                    stream_callback=lambda sid, toks: first.append(time.perf_counter()) if not first else None)
-    ttft_first_sighting = (first[0] - t0) * 1e3
+    ttft_first_sighting = None
+    if args.full:
+        guard.stage("ttft_first_sighting")
+        first = []
+        sync_all()
+        t0 = time.perf_counter()
+        engine.generate([prompt[:-1]], SamplingParams(temperature=0, ignore_eos=True, max_new_tokens=1), use_tqdm=False,
+                        stream_callback=lambda sid, toks: first.append(time.perf_counter()) if not first else None)
+        ttft_first_sighting = (first[0] - t0) * 1e3
     ttft_round_p50 = statistics.median(ttfts_round[2:] if len(ttfts_round) > 2 else ttfts_round[-1:])
 
     # ---- timed decode steps through the real engine ----
@@ -587,11 +616,13 @@ def run(args, guard, rank, world):
     hits = list(METRICS["cache_hits"][h0:])
     seq = engine.scheduler.running[0] if engine.scheduler.running else None
     ctx = len(seq) if seq is not None else args.input_len
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, seq, lens, hits)
     # ---- the reference's own protocol (bench/bench.py:34-51,233-235,351-352): random 128-token prompts, 512 output tokens,
     #      b = 1, temp 0; throughput = output tokens / wall clock of generate() (prefill included) and the decode-only rate
     #      (llm_engine.py:215-223).  Context grows 128 -> 640 here, where the timed steps above sit at ~130-300. ----
     ref = None
-    if args.ref_seqs > 0:
+    if args.full and args.ref_seqs > 0:
         guard.stage("reference_protocol_run")
         engine.abort_all()                       # the timed request is not run to its end
         random.seed(1)
@@ -620,7 +651,8 @@ def run(args, guard, rank, world):
     #      JIT chain on the critical path).  `value` above depends on how well the constructed pair agrees; this does not.  The draft's
     #      weight VALUES are overwritten in place (hipGraphs keep their pointers), the target is untouched. ----
     rand_pair = None
-    if recipe is not None and recipe.get("kind") == "pair" and dr is not None and not dedicated and tp == 1 and not args.no_random_pair:
+    if (args.full and recipe is not None and recipe.get("kind") == "pair" and dr is not None and not dedicated and tp == 1
+            and not args.no_random_pair):
         guard.stage("random_pair_steps")
         from ssd_amd import weights as W
         engine.abort_all()
@@ -695,7 +727,8 @@ def run(args, guard, rank, world):
         # round later -- that figure is kept beside it
         "ttft_after_first_round_p50_ms": round(ttft_round_p50, 3),
         # eager prefill of a prompt length met for the first time (warm process); `ttft_cold_process_ms` = the very first request
-        "ttft_first_sighting_ms": round(ttft_first_sighting, 3), "ttft_cold_process_ms": round(ttfts[0], 3),
+        "ttft_first_sighting_ms": None if ttft_first_sighting is None else round(ttft_first_sighting, 3),
+        "ttft_cold_process_ms": round(ttfts[0], 3),
         # the reference's own protocol (2 x 128 -> 512 tokens, prefill included, context -> 640): THE tokens/s to quote
         "value_reference_protocol": None if ref is None else ref["tokens_per_s_total"],
         # the floor: the same engine and step with an independent draft (mean accepted length ~ 1): tokens/s that does not depend on the pair
@@ -708,6 +741,9 @@ def run(args, guard, rank, world):
         "tokens_per_s_at_accepted_len": {str(a): round(a / (dt / args.steps), 1) for a in (1, 2, 4, K + 1)},
         "reference_protocol": ref,
     }
+    if not args.full:                 # measured by --full only: a plain line does not carry them
+        for k_ in ("ttft_first_sighting_ms", "value_reference_protocol", "value_random_pair", "random_pair", "reference_protocol"):
+            del out[k_]
     if world > 1:                     # first contact with a multi-GPU box: say up front which transport carries the sums and how far the
         # first-run paths of DESIGN.md section 7 got (a failure record carries the same two fields)
         out = {"collective_one_shot_status": getattr(engine.model_runner, "custom_ar_status", None),
@@ -715,7 +751,7 @@ def run(args, guard, rank, world):
         if rank == 0:
             print(f"[ssd bench] n_gpus {world}: one-shot all-reduce: {out['collective_one_shot_status']}; first-run paths completed: "
                   f"{out['first_run_paths']['completed']}", file=sys.stderr, flush=True)
-    if not args.no_roofline:          # every rank launches the same sequence (shard shapes); rank 0 reports
+    if args.full and not args.no_roofline:          # every rank launches the same sequence (shard shapes); rank 0 reports
         guard.stage("roofline_probe")
         with torch.inference_mode():      # the engine's buffers are inference tensors (ModelRunner runs under inference_mode)
             roof = gemm_roofline(legs)
@@ -723,8 +759,8 @@ def run(args, guard, rank, world):
                 out["collective"] = collective_probe(engine, K + 1)
         out["roofline"] = roof
     if rank == 0:
-        guard.stage("cpu_baseline")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
+            guard.stage("cpu_baseline")
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the baseline must never take the GPU number down with it

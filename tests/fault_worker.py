@@ -15,9 +15,13 @@ def main():
     layout = sys.argv[1]                    # "tp2" | "tp1+draft" | "tp2+draft"
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     fault = dict(kv.split("=") for kv in os.environ.get("SSD_FAULT", "").split(",") if kv)
-    from ssd_amd.utils.watchdog import RunGuard
+    from ssd_amd.utils.watchdog import RunGuard, env_float
+    # Where ranks wait in the same stage for a wedged peer, the first stage limit to pass ends the launch and the launcher
+    # terminates the rest.  Rank 0 writes the line: the other ranks get 5 s more, so that the line reports rank 0's own limit
+    # (equal limits left it to a 0.25 s watchdog tick which rank went first, and rank 0 then read "terminated" now and then).
+    limit = env_float("SSD_STAGE_TIMEOUT_S", 900.0) + (0.0 if rank == 0 else 5.0)
     guard = RunGuard(rank, world, {"metric": "fault-injection worker", "value": None, "unit": "tokens/s", "n_gpus": world,
-                                   "config": {"workload": layout}}).install()
+                                   "config": {"workload": layout}}, stage_timeout=limit).install()
 
     def body():
         import torch
