@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped whenever a signature or a semantic of this header changes; ssd_abi_version() returns the value the library was built
  * with, so a consumer compiled against another header can tell (tests/abi_consumer.c does). */
-#define SSD_HIP_ABI_VERSION 2
+#define SSD_HIP_ABI_VERSION 3
 
 #define SSD_OK 0
 #define SSD_ERR_SHAPE (-1)
@@ -106,13 +106,17 @@ int ssd_gemm_splitk(const void* x_frag, const void* w_frag, const void* bias, vo
 int ssd_gemm_parts(const void* x_frag, const void* w_frag, const void* bias, void* y, void* parts, int M, int N, int K,
                    int ldy, int splits, int waves, void* stream);
 
-/* Prefill-chunk GEMM, 16 < M <= 128 (csrc/gemm_pf.hip): the reference's eager prefill F.linear calls
+/* Prefill GEMM, 16 < M <= 16384 (csrc/gemm_pf.hip): the reference's eager prefill F.linear calls
  * (ssd/engine/model_runner.py:602 -> ssd/layers/linear.py:65,98,196).  Same operands and epilogues (SSD_EPI_ROWS,
  * SSD_EPI_SILU_FRAG) as ssd_gemm_wf; the x tile of a k-step is shared by a workgroup through LDS and K is split
  * across workgroups into fp32 partials in `workspace` (>= ssd_gemm_pf_workspace_bytes), summed in a fixed order.
  * N % 128 == 0, K % 128 == 0; splits <= 0 picks the default.  epilogue 2 (partials only, y may be NULL, no bias): the fp32
  * partials [splits][M][N] in `workspace` ARE the output (splits = ssd_gemm_pf_workspace_bytes(M, N, K) / (4 M N)), to be
- * summed by ssd_rmsnorm_parts -- the add + RMSNorm that follows o_proj / down_proj -- instead of an epilogue launch. */
+ * summed by ssd_rmsnorm_parts -- the add + RMSNorm that follows o_proj / down_proj -- instead of an epilogue launch.
+ * M > 128 (a whole prompt in one launch; since ABI 3): a compute-bound tiled MFMA GEMM (256 x 256 output tiles by default, smaller
+ * ones or a K split when the tile count leaves CUs idle); epilogues 0 and 1 only (2 returns SSD_ERR_ARG); K splits, when picked,
+ * are summed in a fixed order.  ssd_gemm_pf_workspace_bytes(M > 128, N, K) returns the largest workspace any M' in (128, M]
+ * needs -- 0 where no decomposition splits K -- so one buffer sized at the longest prompt serves every shorter one. */
 int ssd_gemm_pf_workspace_bytes(int M, int N, int K, int64_t* bytes);
 int ssd_gemm_pf(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K, int ldy,
                 int epilogue, void* workspace, int64_t workspace_bytes, int splits, void* stream);

@@ -1,4 +1,5 @@
-// Prefill GEMM  y[M,N] = x[M,K] . W[N,K]^T  for 32 < M <= 128 token rows (one prefill chunk).  Replaces the cuBLAS
+// Prefill GEMM  y[M,N] = x[M,K] . W[N,K]^T  for 32 < M <= 128 token rows (one prefill chunk); prompts of 128 < M <= 16384 rows go
+// to the compute-bound tiled kernel further down (gemm_lm_kernel) in one launch.  Replaces the cuBLAS
 // F.linear calls of the reference's eager prefill (ssd/layers/linear.py:65,98,196; model_runner.py:602).
 //
 // Still HBM-bound on MI355X (128 FLOP/B against a ridge of ~312), but unlike the skinny kernel (gemm.hip) the x
@@ -15,6 +16,7 @@
 //    atomics), adds the bias, rounds once to bf16 and applies the same epilogues as gemm.hip (rows | SiLU*mul ->
 //    fragment-major).  The partials are ~6-25 % extra traffic and mostly live in the 256 MiB Infinity Cache.
 #include "common.h"
+#include <algorithm>
 #include <cstdlib>
 
 enum { PF_EPI_ROWS = 0, PF_EPI_SILU_FRAG = 1, PF_EPI_PARTIALS = 2 };
@@ -336,8 +338,266 @@ static void pf_refine(int M, int N, int K, int splits, int* waves, int* bps) {
   if (N % (16 * 2 * 5) == 0 && ((N / (16 * 2 * 5)) * splits) % 256 == 0) *waves = 5;
 }
 
+// ============================================================================================================================
+// Long prefill, 128 < M <= 16384 (a whole prompt in one launch per matrix).  At these M the GEMM is compute-bound (2 M FLOP per
+// weight byte against a ridge of ~312), so the kernel is the classic LDS-tiled MFMA GEMM instead of the weight-streaming one above:
+//  * a workgroup owns a BM x BN output tile (BM x rows by BN W rows; 256 x 256 with 8 waves by default) and walks K in stages of
+//    BK = 64 (two 32-deep k-steps);
+//  * both operands are already 1 KiB fragment tiles (16 rows x 32 k in MFMA-16x16x32 lane order), so ONE global_load_lds of 16 B
+//    per lane copies a tile into LDS in exactly the order a lane-linear ds_read_b128 reads it back as an MFMA operand: no
+//    transpose, no swizzle, and a lane-linear b128 read of 1 KiB is bank-conflict free;
+//  * two LDS buffers, ONE barrier per stage: the stage after the barrier is staged by LDS-DMA while the current one is multiplied;
+//    a raw s_barrier (not __syncthreads, whose fence would drain the DMA early) and all LDS in one __shared__ array;
+//  * row groups past ceil(M/16) (x) or N/16 (W) are clamped to the last valid group for the loads and never stored: the kernel
+//    reads only inside both operands and writes no y row >= M and no column >= N;
+//  * workgroups are remapped so that consecutive tile ids share an XCD (bijective for any count) and walk M fastest, so the W
+//    tile of a column is re-read from that XCD's L2;
+//  * K may be split over workgroups (only when the tile count leaves most CUs idle): fp32 partials ws[z][m][n], summed in order by
+//    gemm_pf_epilogue_kernel -- deterministic, no atomics.  Unsplit, the epilogue (bias in fp32, one rounding) runs in place.
+typedef __attribute__((address_space(1))) void* lm_gptr_t;
+typedef __attribute__((address_space(3))) void* lm_lptr_t;
+constexpr int LM_MAX_M = 16384;
+constexpr int LM_CUS = 256;
+
+template <int BM, int BN, int WM, int WN, int DIRECT>
+__global__ void __launch_bounds__(64 * WM * WN, 1)
+gemm_lm_kernel(const u32x4_t* __restrict__ Wf, const u32x4_t* __restrict__ Xf, float* __restrict__ ws, int M, int N, int K,
+               int nkb, int tiles_m, int tiles_n, const bf16_t* __restrict__ bias, void* __restrict__ Yv, int ldy) {
+  constexpr int NW = WM * WN;
+  constexpr int TW = BN / 16, TX = BM / 16, TT = TW + TX;      // fragment tiles per k-step: W groups first, then x groups
+  constexpr int G = 2 * TT / NW;                               // LDS-DMA tiles each wave stages per BK = 64 stage
+  constexpr int MTW = TX / WM, NTW = TW / WN;                  // x / W row groups of one wave's output block
+  static_assert((2 * TT) % NW == 0 && TX % WM == 0 && TW % WN == 0 && NTW % 2 == 0, "tile geometry");
+  __shared__ u32x4_t lds[2][2][TT][64];                        // [buffer][k-step][tile][lane]: the only LDS object
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+  const int KT = K >> 5;
+
+  // XCD remap: hardware places workgroup `orig` on XCD orig % 8; give each XCD a contiguous run of tile ids
+  const int nwg = gridDim.x, orig = blockIdx.x;
+  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
+  const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  const int tiles = tiles_m * tiles_n;
+  const int z = wgid / tiles, t = wgid - z * tiles;
+  const int mg0 = (t % tiles_m) * TX, ng0 = (t / tiles_m) * TW;
+  const int mg_valid = (M + 15) >> 4, ng_valid = N >> 4;
+  const int kt0 = z * nkb * 2;
+
+  // source of each tile this wave stages (clamped row groups: always inside the operand)
+  const u32x4_t* src[G];
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    const int j = wave * G + i, tt = j % TT, ks = j / TT;
+    const int grp = tt < TW ? min(ng0 + tt, ng_valid - 1) : min(mg0 + tt - TW, mg_valid - 1);
+    src[i] = (tt < TW ? Wf : Xf) + (((size_t)grp * KT + kt0 + ks) << 6) + lane;
+  }
+  auto issue = [&](int kb, int buf) {
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      const int j = wave * G + i;
+      __builtin_amdgcn_global_load_lds((lm_gptr_t)(src[i] + ((size_t)kb << 7)), (lm_lptr_t)&lds[buf][j / TT][j % TT][0], 16, 0, 0);
+    }
+  };
+
+  f32x4_t acc[NTW][MTW];
+#pragma unroll
+  for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt) acc[nt][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  issue(0, 0);
+  for (int kb = 0; kb < nkb; ++kb) {
+    const int cur = kb & 1;
+    // RAW: this wave's DMA of stage kb has landed, and after the barrier every wave's has.  WAR: every wave finished reading
+    // buffer cur ^ 1 (stage kb - 1) before the barrier, so it may be restaged right after it.
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (kb + 1 < nkb) issue(kb + 1, cur ^ 1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      u32x4_t a[NTW], b[MTW];
+#pragma unroll
+      for (int nt = 0; nt < NTW; ++nt) a[nt] = lds[cur][ks][wn * NTW + nt][lane];
+#pragma unroll
+      for (int mt = 0; mt < MTW; ++mt) b[mt] = lds[cur][ks][TW + wm * MTW + mt][lane];
+#pragma unroll
+      for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) acc[nt][mt] = mfma16(a[nt], b[mt], acc[nt][mt]);
+    }
+  }
+
+  const int mcol = lane & 15, nrow = (lane >> 4) * 4;
+  const int gm0 = mg0 + wm * MTW, gn0 = ng0 + wn * NTW;       // first x / W row group of this wave's block
+  if constexpr (DIRECT == 1) {
+#pragma unroll
+    for (int nt = 0; nt < NTW; ++nt) {
+      if (gn0 + nt >= ng_valid) continue;
+      const int n = (gn0 + nt) * 16 + nrow;
+      float bv[4] = {0.f, 0.f, 0.f, 0.f};
+      if (bias) {
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) bv[r4] = bf2f(bias[n + r4]);
+      }
+#pragma unroll
+      for (int mt = 0; mt < MTW; ++mt) {
+        const int m = (gm0 + mt) * 16 + mcol;
+        f32x4_t s = acc[nt][mt];
+        if (bias) {
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) s[r4] += bv[r4];
+        }
+        if (m < M) {
+          const u32x2_t v = {pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3])};
+          *reinterpret_cast<u32x2_t*>(reinterpret_cast<bf16_t*>(Yv) + (size_t)m * ldy + n) = v;
+        }
+      }
+    }
+  } else if constexpr (DIRECT == 2) {
+    // W row groups come in (gate, up) pairs (gn0 is even); act = silu(bf16(g)) * bf16(u), one rounding, fragment-major (K' = N/2)
+    const int KT2 = (N >> 1) >> 5;
+    u32x2_t* out2 = reinterpret_cast<u32x2_t*>(Yv);
+#pragma unroll
+    for (int pr = 0; pr < NTW / 2; ++pr) {
+      const int gg = gn0 + 2 * pr;
+      if (gg >= ng_valid) continue;
+      const int f = (gg >> 1) * 16 + nrow;
+      const int ng = gg * 16 + nrow, nu = ng + 16;
+#pragma unroll
+      for (int mt = 0; mt < MTW; ++mt) {
+        const int m = (gm0 + mt) * 16 + mcol;
+        float o[4];
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          float gb = acc[2 * pr][mt][r4], ub = acc[2 * pr + 1][mt][r4];
+          if (bias) { gb += bf2f(bias[ng + r4]); ub += bf2f(bias[nu + r4]); }
+          gb = round_bf(gb); ub = round_bf(ub);
+          o[r4] = (gb / (1.0f + __expf(-gb))) * ub;
+        }
+        if (m < M) {
+          const u32x2_t v = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
+          out2[frag_chunk(m, f >> 3, KT2) * 2 + ((f >> 2) & 1)] = v;
+        }
+      }
+    }
+  } else {
+    float* out = ws + (size_t)z * M * N;
+#pragma unroll
+    for (int nt = 0; nt < NTW; ++nt) {
+      if (gn0 + nt >= ng_valid) continue;
+      const int n = (gn0 + nt) * 16 + nrow;
+#pragma unroll
+      for (int mt = 0; mt < MTW; ++mt) {
+        const int m = (gm0 + mt) * 16 + mcol;
+        if (m < M) *reinterpret_cast<f32x4_t*>(out + (size_t)m * N + n) = acc[nt][mt];
+      }
+    }
+  }
+}
+
+// Tile forms of the long-prefill kernel (ssd_gemm_pf_cfg nt bits 0..7 at M > 128): 1 = 256 x rows x 256 W rows (8 waves, 128 KiB
+// LDS), 2 = 128 x 256 (8 waves), 3 = 256 x 128 (8 waves), 4 = 128 x 128 (4 waves, 64 KiB: two workgroups per CU).
+constexpr int LM_FORMS = 4;
+static const int lm_bm[LM_FORMS] = {256, 128, 256, 128}, lm_bn[LM_FORMS] = {256, 256, 128, 128}, lm_occ[LM_FORMS] = {1, 1, 1, 2};
+
+static int64_t lm_tiles(int form, int M, int N) {
+  return (int64_t)((M + lm_bm[form] - 1) / lm_bm[form]) * ((N + lm_bn[form] - 1) / lm_bn[form]);
+}
+
+// Default decomposition: the form with the least estimated time (rounds of resident workgroups x tile work / relative per-CU rate
+// of the smaller tiles), then a K split only when even that form leaves more than half the CUs idle.
+static void lm_pick(int M, int N, int K, int* form_out, int* splits_out) {
+  static const double rel[LM_FORMS] = {1.0, 0.8, 0.8, 0.8};      // fitted to profiles/prefill_gemm_sweep.jsonl (us_by_form)
+  int best = 0;
+  double best_t = 0;
+  for (int f = 0; f < LM_FORMS; ++f) {
+    const int64_t per_round = (int64_t)LM_CUS * lm_occ[f];
+    const double t = (double)((lm_tiles(f, M, N) + per_round - 1) / per_round) * lm_bm[f] * lm_bn[f] * lm_occ[f] / (65536.0 * rel[f]);
+    if (f == 0 || t < best_t - 1e-9) { best = f; best_t = t; }
+  }
+  const int64_t cnt = lm_tiles(best, M, N), slots = (int64_t)LM_CUS * lm_occ[best];
+  const int nkb = K / 64;
+  int s = 1;
+  if (cnt * 2 <= slots)
+    while (s < 8 && cnt * s * 2 <= slots && nkb % (s * 2) == 0 && nkb / (s * 2) >= 8) s *= 2;
+  *form_out = best + 1;
+  *splits_out = s;
+}
+
+static int64_t lm_workspace(int M, int N, int K) {
+  int form, s;
+  lm_pick(M, N, K, &form, &s);
+  return s > 1 ? (int64_t)s * M * N * 4 : 0;
+}
+
+template <int BM, int BN, int WM, int WN>
+static int lm_go(const void* x, const void* w, float* ws, int M, int N, int K, int splits, int direct, const void* bias, void* y,
+                 int ldy, hipStream_t st) {
+  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+  const int nkb = (K / 64) / splits;
+  const dim3 grid((unsigned)(tiles_m * tiles_n * splits)), block(64 * WM * WN);
+#define LM_ARGS (const u32x4_t*)w, (const u32x4_t*)x, ws, M, N, K, nkb, tiles_m, tiles_n, (const bf16_t*)bias, y, ldy
+  if (direct == 1) hipLaunchKernelGGL((gemm_lm_kernel<BM, BN, WM, WN, 1>), grid, block, 0, st, LM_ARGS);
+  else if (direct == 2) hipLaunchKernelGGL((gemm_lm_kernel<BM, BN, WM, WN, 2>), grid, block, 0, st, LM_ARGS);
+  else hipLaunchKernelGGL((gemm_lm_kernel<BM, BN, WM, WN, 0>), grid, block, 0, st, LM_ARGS);
+#undef LM_ARGS
+  return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
+}
+
+// M > 128: validated like the chunk path; form 0 / splits <= 0 pick the default.
+static int lm_gemm(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K, int ldy, int epilogue,
+                   void* workspace, int64_t workspace_bytes, int form, int splits, hipStream_t st) {
+  if (M > LM_MAX_M || N <= 0 || K <= 0 || N % 128 != 0 || K % 128 != 0) return SSD_ERR_SHAPE;
+  if (epilogue != PF_EPI_ROWS && epilogue != PF_EPI_SILU_FRAG) return SSD_ERR_ARG;     // PF_EPI_PARTIALS: M <= 128 only
+  if (form < 0 || form > LM_FORMS) return SSD_ERR_ARG;
+  int dform, dsplits;
+  lm_pick(M, N, K, &dform, &dsplits);
+  if (form == 0) form = dform;
+  if (splits <= 0) splits = dform == form ? dsplits : 1;
+  if (splits > 16 || (K / 64) % splits != 0) return SSD_ERR_ARG;
+  if (!x_frag || !w_frag || !y) return SSD_ERR_ARG;
+  const int direct = splits == 1 ? (epilogue == PF_EPI_ROWS ? 1 : 2) : 0;
+  if (!direct && (!workspace || workspace_bytes < (int64_t)splits * M * N * 4)) return SSD_ERR_ARG;
+  float* ws = (float*)workspace;
+  int rc;
+#define LM_A x_frag, w_frag, ws, M, N, K, splits, direct, bias, y, ldy, st
+  switch (form) {
+    case 1: rc = lm_go<256, 256, 2, 4>(LM_A); break;
+    case 2: rc = lm_go<128, 256, 2, 4>(LM_A); break;
+    case 3: rc = lm_go<256, 128, 4, 2>(LM_A); break;
+    default: rc = lm_go<128, 128, 2, 2>(LM_A); break;
+  }
+#undef LM_A
+  if (rc != SSD_OK || direct) return rc;
+  if (epilogue == PF_EPI_ROWS) {
+    const size_t items = (size_t)M * N / 4;
+    hipLaunchKernelGGL((gemm_pf_epilogue_kernel<PF_EPI_ROWS>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, ws,
+                       (const bf16_t*)bias, y, M, N, splits, ldy);
+  } else {
+    const size_t items = (size_t)M * (N / 2) / 4;
+    hipLaunchKernelGGL((gemm_pf_epilogue_kernel<PF_EPI_SILU_FRAG>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, ws,
+                       (const bf16_t*)bias, y, M, N, splits, ldy);
+  }
+  return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
+}
+
 extern "C" int ssd_gemm_pf_workspace_bytes(int M, int N, int K, int64_t* bytes) {
   if (!bytes || M <= 0 || N <= 0 || K <= 0 || N % (16 * 2 * PF_WAVES_DEFAULT) != 0) return SSD_ERR_ARG;
+  if (M > 128) {
+    // the long-prefill path: the LARGEST workspace any M' in (128, M] needs (0 where none splits K), so that a buffer sized at the
+    // longest prompt serves every shorter one.  The decomposition is constant inside each 128-row band, where the need grows with M'.
+    if (M > LM_MAX_M || K % 128 != 0) return SSD_ERR_ARG;
+    int64_t need = 0;
+    for (int m = 256;; m += 128) {
+      const int mm = m < M ? m : M;
+      need = std::max(need, lm_workspace(mm, N, K));
+      if (mm == M) break;
+    }
+    *bytes = need;
+    return SSD_OK;
+  }
   int nt, splits;
   pf_pick(N, K, &nt, &splits);
   *bytes = (int64_t)splits * M * N * 4;
@@ -347,6 +607,8 @@ extern "C" int ssd_gemm_pf_workspace_bytes(int M, int N, int K, int64_t* bytes) 
 extern "C" int ssd_gemm_pf_cfg(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K,
                                int ldy, int epilogue, void* workspace, int64_t workspace_bytes, int nt, int splits,
                                void* stream) {
+  if (M > 128) return lm_gemm(x_frag, w_frag, bias, y, M, N, K, ldy, epilogue, workspace, workspace_bytes, nt & 0xff, splits,
+                              (hipStream_t)stream);
   if (M <= 16 || M > 128 || N <= 0 || K <= 0 || (K % (32 * PF_U))) return SSD_ERR_SHAPE;
   if (epilogue != PF_EPI_ROWS && epilogue != PF_EPI_SILU_FRAG && epilogue != PF_EPI_PARTIALS) return SSD_ERR_ARG;
   if (epilogue == PF_EPI_PARTIALS && bias) return SSD_ERR_ARG;
@@ -393,6 +655,7 @@ extern "C" int ssd_gemm_pf_cfg(const void* x_frag, const void* w_frag, const voi
 extern "C" int ssd_gemm_pf(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K,
                            int ldy, int epilogue, void* workspace, int64_t workspace_bytes, int splits, void* stream) {
   if (N <= 0 || K <= 0 || N % (16 * 2 * PF_WAVES_DEFAULT) != 0) return SSD_ERR_SHAPE;
+  if (M > 128) return lm_gemm(x_frag, w_frag, bias, y, M, N, K, ldy, epilogue, workspace, workspace_bytes, 0, splits, (hipStream_t)stream);
   int nt, s, waves, bps;
   pf_pick(N, K, &nt, &s, &waves);
   if (splits > 0) { s = splits; waves = 4; }

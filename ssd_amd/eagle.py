@@ -42,6 +42,10 @@ class HipEagleDraft(HipDecoder):
         self.buf_actsf = z(H.frag_numel(T, self.A))
         self.logits_d = z(self.max_logit_rows, self.Vd)
         self.logits.fill_(float("-inf"))
+        if self._lm_ok:         # the draft's own long-prefill shapes: QKV over K = 2h, fc, the draft-vocabulary head
+            need = max(self._lm_ws_numel(n, k) for n, k in ((self.qkv_n, 2 * h), (h, self.A), (self.Vd, h)))
+            if need > self._ws_pf.numel():
+                self._ws_pf = z(need, dtype=torch.float32)
         self.target_index: torch.Tensor | None = None
 
     def load_weights(self, weight_iter) -> None:

@@ -16,7 +16,7 @@ _LIB = None
 
 c_void_p, c_int, c_long, c_float, c_int64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_int64
 
-ABI_VERSION = 2       # include/ssd_hip.h SSD_HIP_ABI_VERSION (tests/test_abi.py compares the two)
+ABI_VERSION = 3       # include/ssd_hip.h SSD_HIP_ABI_VERSION (tests/test_abi.py compares the two)
 
 # name -> argtypes, exactly include/ssd_hip.h (+ include/ssd_hip_tune.h)
 SIGNATURES = {

@@ -106,7 +106,10 @@ def gemm_pf_workspace_bytes(M: int, N: int, K: int) -> int:
 
 def gemm_pf(x_frag, w_frag, y, M: int, N: int, K: int, ldy: int, workspace, epilogue: int = EPI_ROWS, bias=None, splits: int = 0,
             nt: int = 0):
-    """Prefill-chunk GEMM (16 < M <= 128); workspace: a float32 device tensor of >= gemm_pf_workspace_bytes."""
+    """Prefill GEMM (16 < M <= 16384); workspace: a float32 device tensor of >= gemm_pf_workspace_bytes.
+
+    M <= 128 is one prefill chunk on the weight-streaming kernels; M > 128 is a whole prompt on the compute-bound tiled
+    kernel (epilogues EPI_ROWS / EPI_SILU_FRAG only; nt selects its tile form 1..4 for sweeps, 0 = default)."""
     wb = workspace.numel() * workspace.element_size()
     if nt:
         _check(load_library().ssd_gemm_pf_cfg(_p(x_frag), _p(w_frag), _p(bias), _p(y), M, N, K, ldy, epilogue, _p(workspace),

@@ -163,7 +163,12 @@ class HipDecoder:
         # path (layer matrices and the LM head): prefill hipGraphs bake this pointer, so it must never be reallocated
         pf_shapes = [(self.qkv_n, self.h), (self.h, self.qn), (2 * self.I, self.h), (self.h, self.I), (self.V, self.h)]
         need = max([H.gemm_pf_workspace_bytes(128, n, k) // 4 for n, k in pf_shapes if self._pf_eligible(n, k)], default=0)
-        self._ws_pf = z(need, dtype=torch.float32) if need and max_tokens > 32 else None
+        # a whole prompt of >= LM_MIN_TOKENS rows is one gemm_pf launch per linear, whatever the matrix size; the query at
+        # max_tokens covers every shorter prompt (0 where no decomposition splits K)
+        self._lm_ok = max_tokens > 128
+        if self._lm_ok:
+            need = max([need] + [self._lm_ws_numel(n, k) for n, k in pf_shapes])
+        self._ws_pf = z(max(need, 1), dtype=torch.float32) if (need or self._lm_ok) and max_tokens > 32 else None
         st = min(T, max_split_tokens)
         self.ws_o = z(st * self.nh * self.max_splits * self.hd, dtype=torch.float32)
         self.ws_ml = z(st * self.nh * self.max_splits * 2, dtype=torch.float32)
@@ -256,6 +261,21 @@ class HipDecoder:
     def _pf_eligible(cls, N: int, K: int) -> bool:
         return 2 * N * K >= cls.PF_MIN_WEIGHT_BYTES and N % 128 == 0 and K % 128 == 0
 
+    # prompts of at least this many rows run every linear as ONE long-prefill GEMM launch (csrc/gemm_pf.hip gemm_lm_kernel,
+    # compute-bound) instead of a loop of 128-row chunks that re-streams the weights once per chunk
+    LM_MIN_TOKENS = 256
+    LM_MAX_TOKENS = 16384
+
+    @classmethod
+    def _lm_eligible(cls, T: int) -> bool:
+        return cls.LM_MIN_TOKENS <= T <= cls.LM_MAX_TOKENS
+
+    def _lm_ws_numel(self, N: int, K: int) -> int:
+        """fp32 workspace elements the long-prefill GEMM of an N x K matrix needs for any prompt up to max_tokens rows."""
+        if N % 128 or K % 128:
+            return 0
+        return H.gemm_pf_workspace_bytes(min(self.max_tokens, self.LM_MAX_TOKENS), N, K) // 4
+
     def _gemm_chunk(self, xf, K, w, N, y, m, ldy, epi, bias):
         """One <= 128-row chunk.  Prefill-sized chunks of a big matrix go to the LDS-shared / split-K kernel
         (csrc/gemm_pf.hip): measured on MI355X at M = 128, 70B layer GEMMs 611 -> 383 us, 8B gate_up 83 -> 62 us; small
@@ -282,6 +302,10 @@ class HipDecoder:
         return S
 
     def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None):
+        if T > 128 and self._lm_eligible(T) and N % 128 == 0 and K % 128 == 0:
+            assert self._ws_pf is not None and self._ws_pf.numel() * 4 >= H.gemm_pf_workspace_bytes(T, N, K), (T, N, K)
+            H.gemm_pf(xf, w, y, T, N, K, ldy, self._ws_pf, epilogue=epi, bias=bias)
+            return
         if T <= 128:
             self._gemm_chunk(xf, K, w, N, y, T, ldy, epi, bias)
             return
