@@ -74,6 +74,11 @@ class Config:
     num_draft_kvcache_blocks: int = -1      # -1: size from free memory like the reference (draft_runner.py:27)
     weights_recipe: dict | None = None      # e.g. {"kind": "pair", "shared": 2048, "snr": 8}: see weights._pair_tensor
 
+    # weight-only quantization of the TARGET's decoder linears (not in the reference): None = bf16, "fp8" = OCP e4m3fn codes with one
+    # fp32 scale per output row (ssd_amd/quant.py, csrc/gemm_fp8.hip).  The draft, the embedding, the LM head, the norms, activations
+    # and the KV cache stay bf16.
+    quantization: str | None = None
+
     @property
     def max_blocks(self) -> int:
         return -(-self.max_model_len // self.kvcache_block_size)
@@ -84,6 +89,12 @@ class Config:
 
     def __post_init__(self):
         assert 1 <= self.num_gpus <= 8, "single node only (reference ssd/config.py:55)"
+        if self.quantization not in (None, "fp8"):
+            raise ValueError(f"quantization must be None or 'fp8', got {self.quantization!r}")
+        if self.quantization == "fp8" and self.num_gpus > 1:
+            raise ValueError("quantization='fp8' runs on one GPU only: tensor-parallel fp8 shards are not supported")
+        if self.quantization == "fp8" and self.use_eagle:
+            raise ValueError("quantization='fp8' is not supported with use_eagle=True (EAGLE-3 taps need the bf16 target path)")
         assert self.num_draft_gpus >= 1 and (self.num_draft_gpus == 1 or (self.speculate and self.draft_async)), \
             "num_draft_gpus > 1 needs draft_async"
         if self.hf_config is None:

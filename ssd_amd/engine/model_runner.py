@@ -60,11 +60,14 @@ class ModelRunner:
             from ssd_amd.eagle import HipEagleDraft as model_cls
         # EAGLE-3 target: tap the residual stream entering config.eagle_layers on every forward (reference llama3.py:256-271)
         taps = list(config.eagle_layers) if (eagle and not is_draft) else None
+        # weight-only quantization applies to the target alone; the draft stays bf16
+        quantization = None if is_draft else getattr(config, "quantization", None)
+        qkw = {"quantization": quantization} if quantization else {}
         self.model = model_cls(model_cfg, max_tokens=max_tokens, max_seqs=self.max_bs, max_blocks=self.max_blocks,
                                block_size=self.block_size, max_model_len=config.max_model_len, device=device,
                                tp_rank=tp_rank, tp_size=tp_size, tp_group=tp_group,
                                max_logit_rows=max(self.max_decode_tokens, self.seq_cap),
-                               max_split_tokens=max(256, self.max_decode_tokens), force_collectives=force_collectives, taps=taps)
+                               max_split_tokens=max(256, self.max_decode_tokens), force_collectives=force_collectives, taps=taps, **qkw)
         if weight_source is not None:
             src = weight_source
         elif model_path is not None and W.has_safetensors(model_path) and model_cfg.family == "eagle3":
@@ -72,7 +75,7 @@ class ModelRunner:
             src = W.load_eagle_safetensors(model_cfg, model_path, target_dir=config.model if os.path.isdir(config.model) else None,
                                            out_device=str(device))
         elif model_path is not None and W.has_safetensors(model_path):
-            src = W.load_safetensors(model_cfg, model_path, tp_rank, tp_size, out_device=str(device))
+            src = W.load_safetensors(model_cfg, model_path, tp_rank, tp_size, out_device=str(device), fp8=quantization == "fp8")
         else:
             gd = gen_device or ("cuda" if model_cfg.hidden_size >= 1024 else "cpu")
             src = W.synthetic_weights(model_cfg, weights_seed, config.weights_std, tp_rank, tp_size, gen_device=gd,

@@ -20,6 +20,8 @@ import torch
 import torch.distributed as dist
 
 from ssd_amd.hip import ops as H
+from ssd_amd.hip import quant_ops as Q
+from ssd_amd import quant
 from ssd_amd.model_config import ModelConfig
 
 BF16 = torch.bfloat16
@@ -57,8 +59,15 @@ class HipDecoder:
     def __init__(self, cfg: ModelConfig, *, max_tokens: int, max_seqs: int, max_blocks: int, block_size: int,
                  max_model_len: int, device: torch.device, tp_rank: int = 0, tp_size: int = 1, tp_group=None,
                  max_logit_rows: int | None = None, max_split_tokens: int = 256, force_collectives: bool = False,
-                 taps: list[int] | None = None):
+                 taps: list[int] | None = None, quantization: str | None = None):
         self.cfg, self.device = cfg, device
+        # quantization="fp8": the decoder linears are e4m3 codes + per-row fp32 scales (ssd_amd/quant.py) and run on csrc/gemm_fp8.hip;
+        # every bf16-only fused form (norm prologues, the QKV+RoPE epilogue, split-K slabs, attention + o_proj, the resident chain /
+        # tree segments, prefill partials) is off, so a layer is norm -> GEMM -> RoPE / KV store -> attention -> GEMM -> norm -> GEMM
+        # -> GEMM.  Single rank only (Config refuses the rest).
+        assert quantization in (None, "fp8"), quantization
+        self.fp8 = quantization == "fp8"
+        assert not self.fp8 or (tp_size == 1 and not force_collectives and taps is None), "fp8 targets are single-rank, without taps"
         self.tp_rank, self.tp_size, self.tp_group = tp_rank, tp_size, tp_group
         # force_collectives: issue the RCCL calls even at tp_size == 1 (lets a single-GPU box exercise the
         # collective + hipGraph-capture path that the multi-GPU runs depend on)
@@ -112,6 +121,8 @@ class HipDecoder:
             self.use_parts = False
         self.fuse_attn_o = True
         self.pf_parts = True
+        if self.fp8:
+            self.use_parts = self.fuse_attn_o = self.pf_parts = False
         # the single-token chain (one sequence, T = 1) with everything between two attention launches in ONE resident launch
         # (csrc/chain.hip): 1 + 2 per layer launches instead of 4 per layer
         # Default ("auto"): on at the geometry it was validated and measured at on the MI355X -- Llama-3.2-1B's, the draft of every
@@ -121,7 +132,7 @@ class HipDecoder:
         _cs = os.environ.get("SSD_CHAIN_SEG", "auto")
         _geo = (self.h, self.qn, self.I, self.qkv_n, self.hd)
         _validated = _geo == (2048, 2048, 8192, 3072, 64)
-        self.chain_seg = ((_cs == "1" or (_cs == "auto" and _validated)) and not cfg.qk_norm and tp_size == 1 and not self.use_coll
+        self.chain_seg = ((_cs == "1" or (_cs == "auto" and _validated)) and not cfg.qk_norm and tp_size == 1 and not self.use_coll and not self.fp8
                           and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         # the same segment for 2..30 token rows (csrc/tree_segment.hip): attention + ONE resident launch per layer instead of 7
         # launches.  Measured on MI355X at the 1B draft's geometry (profiles/r05_tree_seg_probe_v1.txt, parity tests/test_hip_tree_segment.py):
@@ -137,7 +148,7 @@ class HipDecoder:
         #  that geometry (tests/test_hip_tree_segment.py) but NOT faster -- a 0.6B layer streams 15 MB, so the segment's fixed edge cost
         #  is all there is: tree step 1.248 -> 1.240 ms at 6 rows, 1.275 -> 1.299 at 12, 1.363 -> 1.457 at 24,
         #  profiles/r05_tree_seg_probe_qwen.txt -- so "auto" leaves it off there)
-        self.tree_seg = ((_ts == "1" or (_ts == "auto" and _validated)) and tp_size == 1 and not self.use_coll
+        self.tree_seg = ((_ts == "1" or (_ts == "auto" and _validated)) and tp_size == 1 and not self.use_coll and not self.fp8
                          and taps is None and max_tokens >= 2
                          and H.tree_segment_ok(2, self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         if self.chain_seg:
@@ -169,6 +180,10 @@ class HipDecoder:
         if self._lm_ok:
             need = max([need] + [self._lm_ws_numel(n, k) for n, k in pf_shapes])
         self._ws_pf = z(max(need, 1), dtype=torch.float32) if (need or self._lm_ok) and max_tokens > 32 else None
+        # fp8 prompts longer than FP8_DIRECT_MAX_T rows: each matrix is dequantized into this bf16 fragment-major scratch, then runs on
+        # the bf16 prefill GEMMs (compute-bound there, so the halved weight bytes buy nothing).  Allocated once: prefill hipGraphs
+        # bake its pointer.
+        self._deq = (z(max(n * k for n, k in pf_shapes[:4])) if self.fp8 and max_tokens > self.FP8_DIRECT_MAX_T else None)
         st = min(T, max_split_tokens)
         self.ws_o = z(st * self.nh * self.max_splits * self.hd, dtype=torch.float32)
         self.ws_ml = z(st * self.nh * self.max_splits * 2, dtype=torch.float32)
@@ -194,8 +209,16 @@ class HipDecoder:
     # ---------------------------------------------------------------------------------------------
     def load_weights(self, weight_iter) -> None:
         """Consumes (name, row-major bf16 shard) pairs; matrices are re-tiled once into the fragment-major
-        layout (gate_up with gate/up row groups interleaved for the fused SiLU epilogue)."""
+        layout (gate_up with gate/up row groups interleaved for the fused SiLU epilogue).  A decoder linear may also come as
+        (name, (q float8_e4m3fn [N, K], s fp32 [N])) from a pre-quantized checkpoint.  An fp8 decoder quantizes each bf16 linear
+        as it arrives (never the whole model in both forms) and stores "<name>" = fp8 frag codes, "<name>_scale" = fp32 [N] in
+        the packed row order."""
         for name, w in weight_iter:
+            if self.fp8 and quant.is_quantized_linear(name):
+                self._load_fp8(name, w)
+                continue
+            if isinstance(w, tuple):            # pre-quantized tensors into a bf16 decoder: compute with bf16(s * q)
+                w = quant.dequantize_fp8(w[0].to(self.device), w[1].to(self.device))
             w = w.to(self.device).contiguous()
             if name.endswith("qkv_proj.weight"):
                 # rotation-paired row order: RoPE pairs share an accumulator tile (fused epilogue) -- layout.hip
@@ -218,6 +241,25 @@ class HipDecoder:
             else:
                 self.w[name] = w
         torch.cuda.synchronize(self.device)
+
+    def _load_fp8(self, name: str, w) -> None:
+        q, s = (w[0].to(self.device), w[1].to(self.device)) if isinstance(w, tuple) else quant.quantize_fp8(w.to(self.device))
+        q, s = q.contiguous(), s.to(torch.float32).reshape(-1).contiguous()
+        N, K = q.shape
+        assert q.dtype == quant.FP8 and s.numel() == N, (name, q.dtype, s.shape)
+        if name.endswith("qkv_proj.weight"):
+            row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd)
+        elif name.endswith("gate_up_proj.weight"):
+            row_map = quant.gate_up_row_map(N)
+        else:
+            row_map = None
+        out = torch.empty(N * K, dtype=torch.uint8, device=self.device)
+        if row_map is not None:
+            row_map = row_map.to(self.device)
+            s = s[row_map.long()].contiguous()
+        Q.fp8_rows_to_frag(q.view(torch.uint8), out, N, K, row_map=row_map)
+        self.w[name] = out
+        self.w[name + "_scale"] = s
 
     def overwrite_weights(self, weight_iter) -> None:
         """New VALUES into the existing weight tensors (same names and shapes): captured hipGraphs keep pointing at the same memory, so a
@@ -242,7 +284,7 @@ class HipDecoder:
         return torch.tensor(idx, dtype=torch.int64)
 
     def weight_bytes(self) -> int:
-        """HBM bytes one forward must stream (every matrix once; the embedding table is only gathered)."""
+        """HBM bytes one forward must stream (every matrix once; the embedding table is only gathered; fp8 codes + their scales)."""
         return sum(t.numel() * t.element_size() for n, t in self.w.items() if n != "model.embed_tokens.weight")
 
     def kv_block_bytes(self) -> int:
@@ -265,6 +307,8 @@ class HipDecoder:
     # compute-bound) instead of a loop of 128-row chunks that re-streams the weights once per chunk
     LM_MIN_TOKENS = 256
     LM_MAX_TOKENS = 16384
+    # fp8 linears of up to this many rows run on the fp8 GEMM itself; longer prompts dequantize into self._deq first
+    FP8_DIRECT_MAX_T = 128
 
     @classmethod
     def _lm_eligible(cls, T: int) -> bool:
@@ -301,7 +345,13 @@ class HipDecoder:
         H.gemm_pf(xf, w, None, T, N, K, N, self._ws_pf, epilogue=H.PF_EPI_PARTIALS)
         return S
 
-    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None):
+    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None):
+        if scale is not None:           # fp8 codes (w) + row scales
+            if T <= self.FP8_DIRECT_MAX_T:
+                Q.gemm_fp8(xf, w, scale, y, T, N, K, ldy, epi, bias)
+                return
+            Q.fp8_dequant_frag(w, scale, self._deq, N, K)
+            w = self._deq
         if T > 128 and self._lm_eligible(T) and N % 128 == 0 and K % 128 == 0:
             assert self._ws_pf is not None and self._ws_pf.numel() * 4 >= H.gemm_pf_workspace_bytes(T, N, K), (T, N, K)
             H.gemm_pf(xf, w, y, T, N, K, ldy, self._ws_pf, epilogue=epi, bias=bias)
@@ -416,7 +466,7 @@ class HipDecoder:
         between producer and norm: the prologue is paid by EVERY workgroup and its LDS image limits residency --
         measured on MI355X, M=7 x K=4096 made gate_up 73 us vs 49 us unfused, M=1 x K=2048 made norm+qkv+rope 5.6 us
         vs 14.8 us."""
-        small = T <= 16 and not self.cfg.qk_norm
+        small = T <= 16 and not self.cfg.qk_norm and not self.fp8
         return small, small and not self.use_coll and T * self.h // 8 <= 1024
 
     def chain_plan(self, T: int, meta: AttnMeta, splits: int) -> bool:
@@ -524,7 +574,7 @@ class HipDecoder:
             else:
                 H.rmsnorm(h, w[p + "input_layernorm.weight"], cfg.rms_norm_eps, T, self.h, res_in=None if li == 0 else res,
                           res_out=res, out_frag=xf)
-        if small or (16 < T <= 32 and not cfg.qk_norm):      # T in 17..32 (tree-decode step): the two-token-tile variant
+        if small or (16 < T <= 32 and not cfg.qk_norm and not self.fp8):      # T in 17..32 (tree-decode step): the two-token-tile variant
             H.gemm_fused(w[p + "self_attn.qkv_proj.weight"], T, self.qkv_n, self.h, H.FEPI_QKV_ROPE, x_frag=xf,
                          bias=w.get(p + "self_attn.qkv_proj.bias"), **rope)
         elif (not gemm_only and w.get(p + "self_attn.qkv_proj.bias") is None and self._pf_partials_ok(T, self.qkv_n, self.h)
@@ -537,7 +587,7 @@ class HipDecoder:
                                   k_norm_w=w.get(p + "self_attn.k_norm.weight"), eps=cfg.rms_norm_eps, qkv_perm=1)
         else:
             self._gemm(xf, self.h, w[p + "self_attn.qkv_proj.weight"], self.qkv_n, self.buf_qkv, T, self.qkv_n,
-                       bias=w.get(p + "self_attn.qkv_proj.bias"))
+                       bias=w.get(p + "self_attn.qkv_proj.bias"), scale=w.get(p + "self_attn.qkv_proj.weight_scale"))
             if gemm_only:
                 return
             H.rope_store_kv(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
@@ -547,13 +597,14 @@ class HipDecoder:
     def launch_o(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> int:
         """Returns the number of split-K slabs left in the prefill workspace (pf_partials), else 0."""
         w = self.w[f"model.layers.{li}.self_attn.o_proj.weight"]
+        ws = self.w.get(f"model.layers.{li}.self_attn.o_proj.weight_scale")
         if pf_partials and self._pf_partials_ok(T, self.h, self.qn):
             return self._gemm_pf_partials(self.buf_af, self.qn, w, self.h, T)
         if self.parts_plan(T) if parts is None else parts:
             S, wv = self._parts("o", T)
             H.gemm_parts(self.buf_af, w, T, self.h, self.qn, parts=self.buf_parts_o, splits=S, waves=wv)
         else:
-            self._gemm(self.buf_af, self.qn, w, self.h, self.buf_h, T, self.h)
+            self._gemm(self.buf_af, self.qn, w, self.h, self.buf_h, T, self.h, scale=ws)
         return 0
 
     def launch_gate_up(self, li: int, T: int, gemm_only: bool = False, pre_normed: bool = False, parts: bool | None = None,
@@ -580,17 +631,19 @@ class HipDecoder:
                 else:
                     H.rmsnorm(self.buf_h, w[p + "post_attention_layernorm.weight"], cfg.rms_norm_eps, T, self.h,
                               res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
-            self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG)
+            self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG,
+                       scale=w.get(p + "mlp.gate_up_proj.weight_scale"))
 
     def launch_down(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> int:
         w = self.w[f"model.layers.{li}.mlp.down_proj.weight"]
+        ws = self.w.get(f"model.layers.{li}.mlp.down_proj.weight_scale")
         if pf_partials and self._pf_partials_ok(T, self.h, self.I):
             return self._gemm_pf_partials(self.buf_actf, self.I, w, self.h, T)
         if self.parts_plan(T) if parts is None else parts:
             S, wv = self._parts("d", T)
             H.gemm_parts(self.buf_actf, w, T, self.h, self.I, parts=self.buf_parts_d, splits=S, waves=wv)
         else:
-            self._gemm(self.buf_actf, self.I, w, self.h, self.buf_h, T, self.h)
+            self._gemm(self.buf_actf, self.I, w, self.h, self.buf_h, T, self.h, scale=ws)
         return 0
 
     def forward(self, input_ids: torch.Tensor, positions: torch.Tensor, T: int, meta: AttnMeta) -> None:

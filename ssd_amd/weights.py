@@ -362,18 +362,73 @@ def load_eagle_safetensors(cfg: ModelConfig, model_dir: str, target_dir: str | N
         yield name, (w.to(out_device) if out_device is not None else w)
 
 
+def checkpoint_quantization(model_dir: str) -> str | None:
+    """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales (config.json
+    quantization_config), None for an unquantized one; every other quantization format is refused here, before any tensor is read."""
+    import json
+    path = os.path.join(model_dir, "config.json")
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        qc = json.load(f).get("quantization_config")
+    if not qc:
+        return None
+    method = qc.get("quant_method")
+    if method != "compressed-tensors":
+        raise ValueError(f"unsupported quantization_config.quant_method {method!r}: only compressed-tensors float8 checkpoints "
+                         "(per-channel or per-tensor weight scales) can be loaded")
+    groups = qc.get("config_groups") or {}
+    if not groups:
+        raise ValueError("compressed-tensors checkpoint without config_groups")
+    for gname, g in groups.items():
+        wq = g.get("weights") or {}
+        if wq.get("type") != "float" or wq.get("num_bits") != 8 or wq.get("strategy") not in ("channel", "tensor"):
+            raise ValueError(f"unsupported compressed-tensors weight scheme in {gname}: {wq} (supported: type float, num_bits 8, "
+                             "strategy channel or tensor)")
+    return "fp8"
+
+
 def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 1,
-                     out_device: str | None = None) -> Iterator[tuple[str, torch.Tensor]]:
+                     out_device: str | None = None, fp8: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
+    """Yields (name, bf16 tensor).  From a compressed-tensors fp8 checkpoint (checkpoint_quantization), a quantized decoder linear
+    comes as (name, (q float8_e4m3fn [N, K], s fp32 [N])) when ``fp8`` (the consumer is an fp8 target: no re-quantization) and as
+    bf16(s * q) otherwise.  Per-tensor scales of the packed q / k / v and gate / up are expanded to one per row before the packing;
+    input_scale tensors (activation quantization) are ignored; unquantized tensors (e.g. the LM head) load as bf16."""
     from safetensors import safe_open
+    from ssd_amd.quant import FP8, dequantize_fp8
+    ckpt_fp8 = checkpoint_quantization(model_dir) == "fp8"
     index: dict[str, str] = {}
     for f in sorted(glob.glob(os.path.join(model_dir, "*.safetensors"))):
         with safe_open(f, "pt", "cpu") as sf:
             for k in sf.keys():
                 index[k] = f
+    if any(k.endswith("weight_scale_inv") for k in index):
+        raise ValueError("block-scaled fp8 checkpoints (weight_scale_inv) are not supported: use per-channel or per-tensor scales")
+    assert not (fp8 and tp > 1), "fp8 targets are single-rank"
 
-    def get(name: str) -> torch.Tensor:
+    def raw(name: str) -> torch.Tensor:
         with safe_open(index[name], "pt", "cpu") as sf:
-            return sf.get_tensor(name).to(BF16)
+            return sf.get_tensor(name)
+
+    def get(name: str):
+        t = raw(name)
+        if t.dtype == FP8:
+            if not ckpt_fp8:
+                raise ValueError(f"{name} is float8_e4m3fn but config.json declares no compressed-tensors quantization")
+            s = raw(name + "_scale").float()
+            N = t.shape[0]
+            if s.numel() == 1:
+                s = s.reshape(1).expand(N).contiguous()
+            elif tuple(s.shape) in ((N, 1), (N,)):
+                s = s.reshape(N).contiguous()
+            else:
+                raise ValueError(f"{name}_scale has shape {tuple(s.shape)}: expected a scalar or [{N}, 1]")
+            return t, s
+        if t.dtype.is_floating_point and t.element_size() == 1:
+            raise ValueError(f"{name} is {t.dtype}: only OCP float8_e4m3fn weights are supported (not fnuz / e5m2)")
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{name} is {t.dtype}: integer-quantized weights are not supported")
+        return t.to(BF16)
 
     def packed_sources(name: str) -> list[str] | None:
         if "qkv_proj" in name:
@@ -384,10 +439,17 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
 
     for name, shape in param_shapes(cfg):
         srcs = packed_sources(name)
-        if srcs is not None and name not in index:
-            w = torch.cat([get(s) for s in srcs], dim=0)
+        parts = [get(s) for s in srcs] if srcs is not None and name not in index else [get(name)]
+        if all(isinstance(p, tuple) for p in parts):
+            w = (torch.cat([p[0] for p in parts], dim=0), torch.cat([p[1] for p in parts], dim=0))
         else:
-            w = get(name)
-        assert tuple(w.shape) == tuple(shape), f"{name}: {tuple(w.shape)} != {shape}"
+            w = torch.cat([dequantize_fp8(*p) if isinstance(p, tuple) else p for p in parts], dim=0)
+        if isinstance(w, tuple) and not fp8:
+            w = dequantize_fp8(*w)
+        got = tuple(w[0].shape if isinstance(w, tuple) else w.shape)
+        assert got == tuple(shape), f"{name}: {got} != {shape}"
+        if isinstance(w, tuple):
+            yield name, ((w[0].to(out_device), w[1].to(out_device)) if out_device is not None else w)
+            continue
         w = shard_param(cfg, name, w, rank, tp)
         yield name, (w.to(out_device) if out_device is not None else w)
