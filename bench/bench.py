@@ -66,6 +66,7 @@ def parse_arguments():
     p.add_argument("--dtemp", type=float, default=None)
     p.add_argument("--x", type=float, default=None, help="sampler_x")
     p.add_argument("--fp8", action="store_true", help="FP8 (e4m3, per-row scales) weight-only target: quantization='fp8'")
+    p.add_argument("--w4a16", action="store_true", help="int4 (bf16 scale per row and 128 columns) weight-only target: quantization='w4a16'")
     for name in ("example", "humaneval", "alpaca", "c4", "ultrafeedback", "random", "all", "chat_template", "verbose", "debug",
                  "wandb"):
         p.add_argument(f"--{name}", action="store_true")
@@ -180,8 +181,12 @@ def main():
               max_steps=args.max_steps)
     if args.eagle:
         kw["use_eagle"] = True
+    if args.fp8 and args.w4a16:
+        raise SystemExit("--fp8 and --w4a16 are exclusive")
     if args.fp8:
         kw["quantization"] = "fp8"
+    if args.w4a16:
+        kw["quantization"] = "w4a16"
     if args.flh is not None or args.fl is not None:
         kw["fan_out_list"] = args.flh if args.flh is not None else args.fl
     if args.flm is not None:

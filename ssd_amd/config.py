@@ -75,8 +75,9 @@ class Config:
     weights_recipe: dict | None = None      # e.g. {"kind": "pair", "shared": 2048, "snr": 8}: see weights._pair_tensor
 
     # weight-only quantization of the TARGET's decoder linears (not in the reference): None = bf16, "fp8" = OCP e4m3fn codes with one
-    # fp32 scale per output row (ssd_amd/quant.py, csrc/gemm_fp8.hip).  The draft, the embedding, the LM head, the norms, activations
-    # and the KV cache stay bf16.
+    # fp32 scale per output row (ssd_amd/quant.py, csrc/gemm_fp8.hip), "w4a16" = signed int4 codes with one bf16 scale per output row
+    # and 128-column group (csrc/gemm_w4a16.hip).  The draft, the embedding, the LM head, the norms, activations and the KV cache stay
+    # bf16.
     quantization: str | None = None
 
     @property
@@ -89,12 +90,14 @@ class Config:
 
     def __post_init__(self):
         assert 1 <= self.num_gpus <= 8, "single node only (reference ssd/config.py:55)"
-        if self.quantization not in (None, "fp8"):
-            raise ValueError(f"quantization must be None or 'fp8', got {self.quantization!r}")
-        if self.quantization == "fp8" and self.num_gpus > 1:
-            raise ValueError("quantization='fp8' runs on one GPU only: tensor-parallel fp8 shards are not supported")
-        if self.quantization == "fp8" and self.use_eagle:
-            raise ValueError("quantization='fp8' is not supported with use_eagle=True (EAGLE-3 taps need the bf16 target path)")
+        if self.quantization not in (None, "fp8", "w4a16"):
+            raise ValueError(f"quantization must be None, 'fp8' or 'w4a16', got {self.quantization!r}")
+        if self.quantization is not None and self.num_gpus > 1:
+            raise ValueError(f"quantization={self.quantization!r} runs on one GPU only: tensor-parallel {self.quantization} shards are "
+                             "not supported")
+        if self.quantization is not None and self.use_eagle:
+            raise ValueError(f"quantization={self.quantization!r} is not supported with use_eagle=True (EAGLE-3 taps need the bf16 "
+                             "target path)")
         assert self.num_draft_gpus >= 1 and (self.num_draft_gpus == 1 or (self.speculate and self.draft_async)), \
             "num_draft_gpus > 1 needs draft_async"
         if self.hf_config is None:

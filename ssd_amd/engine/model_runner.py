@@ -75,7 +75,8 @@ class ModelRunner:
             src = W.load_eagle_safetensors(model_cfg, model_path, target_dir=config.model if os.path.isdir(config.model) else None,
                                            out_device=str(device))
         elif model_path is not None and W.has_safetensors(model_path):
-            src = W.load_safetensors(model_cfg, model_path, tp_rank, tp_size, out_device=str(device), fp8=quantization == "fp8")
+            src = W.load_safetensors(model_cfg, model_path, tp_rank, tp_size, out_device=str(device), fp8=quantization == "fp8",
+                                   w4a16=quantization == "w4a16")
         else:
             gd = gen_device or ("cuda" if model_cfg.hidden_size >= 1024 else "cpu")
             src = W.synthetic_weights(model_cfg, weights_seed, config.weights_std, tp_rank, tp_size, gen_device=gd,

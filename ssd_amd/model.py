@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import quant_ops as Q
+from ssd_amd.hip import w4_ops as W4
 from ssd_amd import quant
 from ssd_amd.model_config import ModelConfig
 
@@ -65,9 +66,14 @@ class HipDecoder:
         # every bf16-only fused form (norm prologues, the QKV+RoPE epilogue, split-K slabs, attention + o_proj, the resident chain /
         # tree segments, prefill partials) is off, so a layer is norm -> GEMM -> RoPE / KV store -> attention -> GEMM -> norm -> GEMM
         # -> GEMM.  Single rank only (Config refuses the rest).
-        assert quantization in (None, "fp8"), quantization
+        # quantization="w4a16": int4 codes + one bf16 scale per row and 128-column group (ssd_amd/quant.py), run on csrc/gemm_w4a16.hip,
+        # with the same layer shape as fp8 (self.quantized turns the fused forms off for both).
+        assert quantization in (None, "fp8", "w4a16"), quantization
         self.fp8 = quantization == "fp8"
-        assert not self.fp8 or (tp_size == 1 and not force_collectives and taps is None), "fp8 targets are single-rank, without taps"
+        self.w4 = quantization == "w4a16"
+        self.quantized = self.fp8 or self.w4
+        assert not self.quantized or (tp_size == 1 and not force_collectives and taps is None), \
+            f"{quantization} targets are single-rank, without taps"
         self.tp_rank, self.tp_size, self.tp_group = tp_rank, tp_size, tp_group
         # force_collectives: issue the RCCL calls even at tp_size == 1 (lets a single-GPU box exercise the
         # collective + hipGraph-capture path that the multi-GPU runs depend on)
@@ -82,6 +88,9 @@ class HipDecoder:
         self.V = cfg.vocab_size // tp_size
         self.qkv_n = (self.nh + 2 * self.nkv) * self.hd
         self.qn = self.nh * self.hd
+        if self.w4 and any(k % quant.W4_GROUP for k in (self.h, self.qn, self.I)):
+            raise ValueError(f"quantization='w4a16' needs hidden_size, num_heads * head_dim and intermediate_size to be multiples of "
+                             f"{quant.W4_GROUP} (the group size), got {self.h}, {self.qn}, {self.I}")
         self.block_size, self.max_blocks = block_size, max_blocks
         self.max_tokens = max_tokens
         self.max_logit_rows = max_logit_rows or max_tokens
@@ -121,7 +130,7 @@ class HipDecoder:
             self.use_parts = False
         self.fuse_attn_o = True
         self.pf_parts = True
-        if self.fp8:
+        if self.quantized:
             self.use_parts = self.fuse_attn_o = self.pf_parts = False
         # the single-token chain (one sequence, T = 1) with everything between two attention launches in ONE resident launch
         # (csrc/chain.hip): 1 + 2 per layer launches instead of 4 per layer
@@ -132,7 +141,7 @@ class HipDecoder:
         _cs = os.environ.get("SSD_CHAIN_SEG", "auto")
         _geo = (self.h, self.qn, self.I, self.qkv_n, self.hd)
         _validated = _geo == (2048, 2048, 8192, 3072, 64)
-        self.chain_seg = ((_cs == "1" or (_cs == "auto" and _validated)) and not cfg.qk_norm and tp_size == 1 and not self.use_coll and not self.fp8
+        self.chain_seg = ((_cs == "1" or (_cs == "auto" and _validated)) and not cfg.qk_norm and tp_size == 1 and not self.use_coll and not self.quantized
                           and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         # the same segment for 2..30 token rows (csrc/tree_segment.hip): attention + ONE resident launch per layer instead of 7
         # launches.  Measured on MI355X at the 1B draft's geometry (profiles/r05_tree_seg_probe_v1.txt, parity tests/test_hip_tree_segment.py):
@@ -148,7 +157,7 @@ class HipDecoder:
         #  that geometry (tests/test_hip_tree_segment.py) but NOT faster -- a 0.6B layer streams 15 MB, so the segment's fixed edge cost
         #  is all there is: tree step 1.248 -> 1.240 ms at 6 rows, 1.275 -> 1.299 at 12, 1.363 -> 1.457 at 24,
         #  profiles/r05_tree_seg_probe_qwen.txt -- so "auto" leaves it off there)
-        self.tree_seg = ((_ts == "1" or (_ts == "auto" and _validated)) and tp_size == 1 and not self.use_coll and not self.fp8
+        self.tree_seg = ((_ts == "1" or (_ts == "auto" and _validated)) and tp_size == 1 and not self.use_coll and not self.quantized
                          and taps is None and max_tokens >= 2
                          and H.tree_segment_ok(2, self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         if self.chain_seg:
@@ -183,7 +192,9 @@ class HipDecoder:
         # fp8 prompts longer than FP8_DIRECT_MAX_T rows: each matrix is dequantized into this bf16 fragment-major scratch, then runs on
         # the bf16 prefill GEMMs (compute-bound there, so the halved weight bytes buy nothing).  Allocated once: prefill hipGraphs
         # bake its pointer.
-        self._deq = (z(max(n * k for n, k in pf_shapes[:4])) if self.fp8 and max_tokens > self.FP8_DIRECT_MAX_T else None)
+        # The same scratch serves w4a16 prompts longer than W4_DIRECT_MAX_T rows.
+        direct_max = self.W4_DIRECT_MAX_T if self.w4 else self.FP8_DIRECT_MAX_T
+        self._deq = (z(max(n * k for n, k in pf_shapes[:4])) if self.quantized and max_tokens > direct_max else None)
         st = min(T, max_split_tokens)
         self.ws_o = z(st * self.nh * self.max_splits * self.hd, dtype=torch.float32)
         self.ws_ml = z(st * self.nh * self.max_splits * 2, dtype=torch.float32)
@@ -212,12 +223,18 @@ class HipDecoder:
         layout (gate_up with gate/up row groups interleaved for the fused SiLU epilogue).  A decoder linear may also come as
         (name, (q float8_e4m3fn [N, K], s fp32 [N])) from a pre-quantized checkpoint.  An fp8 decoder quantizes each bf16 linear
         as it arrives (never the whole model in both forms) and stores "<name>" = fp8 frag codes, "<name>_scale" = fp32 [N] in
-        the packed row order."""
+        the packed row order.  Likewise a w4a16 decoder takes bf16 linears or quant.W4Tensor(packed, scale) from a pack-quantized
+        checkpoint and stores "<name>" = w4 frag codes, "<name>_scale" = bf16 w4 frag scales (include/ssd_hip_w4a16.h)."""
         for name, w in weight_iter:
             if self.fp8 and quant.is_quantized_linear(name):
                 self._load_fp8(name, w)
                 continue
-            if isinstance(w, tuple):            # pre-quantized tensors into a bf16 decoder: compute with bf16(s * q)
+            if self.w4 and quant.is_quantized_linear(name):
+                self._load_w4(name, w)
+                continue
+            if isinstance(w, quant.W4Tensor):   # int4 tensors into a bf16 decoder: compute with bf16(s * q)
+                w = quant.dequantize_w4a16(w.packed.to(self.device), w.scale.to(self.device))
+            elif isinstance(w, tuple):          # pre-quantized tensors into a bf16 decoder: compute with bf16(s * q)
                 w = quant.dequantize_fp8(w[0].to(self.device), w[1].to(self.device))
             w = w.to(self.device).contiguous()
             if name.endswith("qkv_proj.weight"):
@@ -261,6 +278,24 @@ class HipDecoder:
         self.w[name] = out
         self.w[name + "_scale"] = s
 
+    def _load_w4(self, name: str, w) -> None:
+        if not isinstance(w, quant.W4Tensor):
+            w = quant.quantize_w4a16(w.to(self.device))
+        packed, s = w.packed.to(self.device).contiguous(), w.scale.to(self.device).to(BF16).contiguous()
+        N, K = packed.shape[0], packed.shape[1] * 8
+        assert packed.dtype == torch.int32 and tuple(s.shape) == (N, K // quant.W4_GROUP), (name, packed.dtype, s.shape)
+        if name.endswith("qkv_proj.weight"):
+            row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
+        elif name.endswith("gate_up_proj.weight"):
+            row_map = quant.gate_up_row_map(N).to(self.device)
+        else:
+            row_map = None
+        q_frag = torch.empty(N * K // 2, dtype=torch.uint8, device=self.device)
+        s_frag = torch.empty(N * K // quant.W4_GROUP, dtype=BF16, device=self.device)
+        W4.w4_rows_to_frag(packed, s, q_frag, s_frag, N, K, row_map=row_map)
+        self.w[name] = q_frag
+        self.w[name + "_scale"] = s_frag
+
     def overwrite_weights(self, weight_iter) -> None:
         """New VALUES into the existing weight tensors (same names and shapes): captured hipGraphs keep pointing at the same memory, so a
         model can be given other weights without recapturing anything (bench.py: the independent-draft leg after the correlated one)."""
@@ -284,7 +319,8 @@ class HipDecoder:
         return torch.tensor(idx, dtype=torch.int64)
 
     def weight_bytes(self) -> int:
-        """HBM bytes one forward must stream (every matrix once; the embedding table is only gathered; fp8 codes + their scales)."""
+        """HBM bytes one forward must stream (every matrix once; the embedding table is only gathered; fp8 or int4 codes + their
+        scales)."""
         return sum(t.numel() * t.element_size() for n, t in self.w.items() if n != "model.embed_tokens.weight")
 
     def kv_block_bytes(self) -> int:
@@ -309,6 +345,8 @@ class HipDecoder:
     LM_MAX_TOKENS = 16384
     # fp8 linears of up to this many rows run on the fp8 GEMM itself; longer prompts dequantize into self._deq first
     FP8_DIRECT_MAX_T = 128
+    # w4a16 linears of up to this many rows run on the w4a16 GEMM itself; longer prompts dequantize into self._deq first
+    W4_DIRECT_MAX_T = 128
 
     @classmethod
     def _lm_eligible(cls, T: int) -> bool:
@@ -346,7 +384,13 @@ class HipDecoder:
         return S
 
     def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None):
-        if scale is not None:           # fp8 codes (w) + row scales
+        if scale is not None and self.w4:   # w4a16 codes (w) + group scales
+            if T <= self.W4_DIRECT_MAX_T:
+                W4.gemm_w4a16(xf, w, scale, y, T, N, K, ldy, epi, bias)
+                return
+            W4.w4_dequant_frag(w, scale, self._deq, N, K)
+            w = self._deq
+        elif scale is not None:         # fp8 codes (w) + row scales
             if T <= self.FP8_DIRECT_MAX_T:
                 Q.gemm_fp8(xf, w, scale, y, T, N, K, ldy, epi, bias)
                 return
@@ -466,7 +510,7 @@ class HipDecoder:
         between producer and norm: the prologue is paid by EVERY workgroup and its LDS image limits residency --
         measured on MI355X, M=7 x K=4096 made gate_up 73 us vs 49 us unfused, M=1 x K=2048 made norm+qkv+rope 5.6 us
         vs 14.8 us."""
-        small = T <= 16 and not self.cfg.qk_norm and not self.fp8
+        small = T <= 16 and not self.cfg.qk_norm and not self.quantized
         return small, small and not self.use_coll and T * self.h // 8 <= 1024
 
     def chain_plan(self, T: int, meta: AttnMeta, splits: int) -> bool:
@@ -574,7 +618,7 @@ class HipDecoder:
             else:
                 H.rmsnorm(h, w[p + "input_layernorm.weight"], cfg.rms_norm_eps, T, self.h, res_in=None if li == 0 else res,
                           res_out=res, out_frag=xf)
-        if small or (16 < T <= 32 and not cfg.qk_norm and not self.fp8):      # T in 17..32 (tree-decode step): the two-token-tile variant
+        if small or (16 < T <= 32 and not cfg.qk_norm and not self.quantized):      # T in 17..32 (tree-decode step): the two-token-tile variant
             H.gemm_fused(w[p + "self_attn.qkv_proj.weight"], T, self.qkv_n, self.h, H.FEPI_QKV_ROPE, x_frag=xf,
                          bias=w.get(p + "self_attn.qkv_proj.bias"), **rope)
         elif (not gemm_only and w.get(p + "self_attn.qkv_proj.bias") is None and self._pf_partials_ok(T, self.qkv_n, self.h)

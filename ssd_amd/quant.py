@@ -1,12 +1,16 @@
-"""FP8 (OCP e4m3fn) weight-only quantization of the decoder linears: W[N, K] ~= s[n] * q[n, k].
+"""Weight-only quantization of the decoder linears: FP8 (OCP e4m3fn) with one scale per row, W[N, K] ~= s[n] * q[n, k], and W4A16
+(int4 with one scale per row and 128-column group, further down).
 
-The one-time load math is torch on the device; the re-tiling into the kernel layout is csrc/gemm_fp8.hip (ssd_fp8_rows_to_frag).
+The one-time load math is torch on the device; the re-tiling into the kernel layout is csrc/gemm_fp8.hip (ssd_fp8_rows_to_frag) and
+csrc/gemm_w4a16.hip (ssd_w4_rows_to_frag).  FP8:
 
     amax[n] = max_k |w[n, k]|                       (fp32)
     inv = 448 / amax,  s = amax / 448               (fp32; an all-zero row gets s = 1, q = 0)
     q = e4m3fn(clamp(fp32(w) * inv, -448, 448))     (round to nearest even, saturating)
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 
@@ -54,3 +58,58 @@ def qkv_row_map(nh: int, nkv: int, hd: int) -> torch.Tensor:
             idx.extend(head * hd + half + 8 * j + i for i in range(8))
     idx.extend(range((nh + nkv) * hd, (nh + 2 * nkv) * hd))
     return torch.tensor(idx, dtype=torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# W4A16: signed int4 codes q in [-8, 7] with one bf16 scale per output row and 128-column group, W ~= s[n, k // 128] * q[n, k]
+# (csrc/gemm_w4a16.hip).  Round to nearest, fp32 on the tensor's device:
+#
+#     amax = max |w| over the group
+#     s = bf16_rne(amax / 7)                          (an all-zero group gets s = 1, q = 0)
+#     q = clamp(rne(w / float(s)), -8, 7)
+#
+# The host form is compressed-tensors "pack-quantized": codes int32 [N, K / 8], word j = columns 8j .. 8j+7, column 8j+i in bits
+# 4i .. 4i+3 as the unsigned nibble q + 8; scales bf16 [N, K / 128].
+# ---------------------------------------------------------------------------------------------------------------------
+W4_GROUP = 128
+
+
+class W4Tensor(NamedTuple):
+    """A W4A16 decoder linear in the pack-quantized host form: packed int32 [N, K / 8], scale bf16 [N, K / 128]."""
+    packed: torch.Tensor
+    scale: torch.Tensor
+
+
+def pack_w4(q: torch.Tensor) -> torch.Tensor:
+    """int codes [N, K] in [-8, 7] -> int32 [N, K / 8] (column 8j+i in bits 4i .. 4i+3 of word j, as q + 8)."""
+    N, K = q.shape
+    u = (q.to(torch.int64) + 8).reshape(N, K // 8, 8)
+    shifts = torch.arange(0, 32, 4, dtype=torch.int64, device=q.device)
+    w = (u << shifts).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def unpack_w4(packed: torch.Tensor) -> torch.Tensor:
+    """int32 [N, K / 8] -> int8 codes [N, K] in [-8, 7]."""
+    N, KW = packed.shape
+    shifts = torch.arange(0, 32, 4, dtype=torch.int64, device=packed.device)
+    u = (packed.to(torch.int64)[..., None] >> shifts) & 0xF
+    return (u - 8).to(torch.int8).reshape(N, KW * 8)
+
+
+def quantize_w4a16(w: torch.Tensor) -> W4Tensor:
+    """[N, K] bf16 (K % 128 == 0) -> W4Tensor(packed int32 [N, K / 8], scale bf16 [N, K / 128]), on w's device."""
+    N, K = w.shape
+    assert K % W4_GROUP == 0, f"W4A16 needs K % {W4_GROUP} == 0, got {K}"
+    wf = w.float().reshape(N, K // W4_GROUP, W4_GROUP)
+    s = (wf.abs().amax(-1) / 7.0).to(torch.bfloat16)
+    s = torch.where(s == 0, torch.ones_like(s), s)
+    q = torch.round(wf / s.float()[..., None]).clamp(-8, 7).reshape(N, K)
+    return W4Tensor(pack_w4(q), s)
+
+
+def dequantize_w4a16(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16(s * q): the weights a W4A16 target computes with, as a bf16 matrix (oracles, a bf16 decoder given int4 tensors)."""
+    q = unpack_w4(packed).float()
+    s = scale.float().repeat_interleave(W4_GROUP, dim=1)
+    return (q * s).to(torch.bfloat16)

@@ -363,8 +363,9 @@ def load_eagle_safetensors(cfg: ModelConfig, model_dir: str, target_dir: str | N
 
 
 def checkpoint_quantization(model_dir: str) -> str | None:
-    """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales (config.json
-    quantization_config), None for an unquantized one; every other quantization format is refused here, before any tensor is read."""
+    """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales, "w4a16" for a
+    pack-quantized one with symmetric int4 weights in groups of 128 columns (config.json quantization_config), None for an
+    unquantized one; every other quantization format is refused here, before any tensor is read."""
     import json
     path = os.path.join(model_dir, "config.json")
     if not os.path.exists(path):
@@ -376,27 +377,58 @@ def checkpoint_quantization(model_dir: str) -> str | None:
     method = qc.get("quant_method")
     if method != "compressed-tensors":
         raise ValueError(f"unsupported quantization_config.quant_method {method!r}: only compressed-tensors float8 checkpoints "
-                         "(per-channel or per-tensor weight scales) can be loaded")
+                         "(per-channel or per-tensor weight scales) and pack-quantized int4 ones (group 128) can be loaded")
     groups = qc.get("config_groups") or {}
     if not groups:
         raise ValueError("compressed-tensors checkpoint without config_groups")
+    kinds = set()
     for gname, g in groups.items():
         wq = g.get("weights") or {}
+        if wq.get("type") == "int" and wq.get("num_bits") == 4:
+            kinds.add(_w4a16_scheme(gname, wq, qc.get("format")))
+            continue
         if wq.get("type") != "float" or wq.get("num_bits") != 8 or wq.get("strategy") not in ("channel", "tensor"):
             raise ValueError(f"unsupported compressed-tensors weight scheme in {gname}: {wq} (supported: type float, num_bits 8, "
-                             "strategy channel or tensor)")
-    return "fp8"
+                             "strategy channel or tensor; or type int, num_bits 4, strategy group, group_size 128)")
+        kinds.add("fp8")
+    if len(kinds) > 1:
+        raise ValueError(f"compressed-tensors checkpoint mixes weight schemes {sorted(kinds)}")
+    return kinds.pop()
+
+
+def _w4a16_scheme(gname: str, wq: dict, fmt) -> str:
+    """The int4 scheme a W4A16 target runs: symmetric, one scale per 128-column group, no activation reordering, pack-quantized."""
+    if fmt != "pack-quantized":
+        raise ValueError(f"unsupported compressed-tensors format {fmt!r} for int4 weights in {gname}: only pack-quantized")
+    if wq.get("symmetric") is not True:
+        raise ValueError(f"asymmetric int4 weights (zero points) in {gname} are not supported: symmetric only")
+    if wq.get("strategy") != "group":
+        raise ValueError(f"unsupported int4 weight strategy {wq.get('strategy')!r} in {gname}: only strategy group")
+    if wq.get("group_size") != 128:
+        raise ValueError(f"unsupported int4 group_size {wq.get('group_size')!r} in {gname}: only 128")
+    if wq.get("actorder") not in (None, False, "static"):
+        raise ValueError(f"int4 weights with actorder {wq.get('actorder')!r} in {gname} are not supported (no g_idx reordering)")
+    return "w4a16"
 
 
 def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 1,
-                     out_device: str | None = None, fp8: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
+                     out_device: str | None = None, fp8: bool = False, w4a16: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
     """Yields (name, bf16 tensor).  From a compressed-tensors fp8 checkpoint (checkpoint_quantization), a quantized decoder linear
     comes as (name, (q float8_e4m3fn [N, K], s fp32 [N])) when ``fp8`` (the consumer is an fp8 target: no re-quantization) and as
     bf16(s * q) otherwise.  Per-tensor scales of the packed q / k / v and gate / up are expanded to one per row before the packing;
-    input_scale tensors (activation quantization) are ignored; unquantized tensors (e.g. the LM head) load as bf16."""
+    input_scale tensors (activation quantization) are ignored; unquantized tensors (e.g. the LM head) load as bf16.
+    From a pack-quantized int4 checkpoint, a quantized linear comes as (name, W4Tensor(packed int32 [N, K/8], scale bf16 [N, K/128]))
+    when ``w4a16`` (codes and bf16 scales bit for bit; fp16 / fp32 scales are rounded to bf16 once) and as bf16(s * q), sharded as
+    usual, otherwise.  A W4A16 checkpoint into an fp8 target and an fp8 one into a W4A16 target are refused."""
     from safetensors import safe_open
-    from ssd_amd.quant import FP8, dequantize_fp8
-    ckpt_fp8 = checkpoint_quantization(model_dir) == "fp8"
+    from ssd_amd.quant import FP8, dequantize_fp8, W4Tensor, dequantize_w4a16
+    assert not (fp8 and w4a16)
+    kind = checkpoint_quantization(model_dir)
+    ckpt_fp8 = kind == "fp8"
+    if kind == "w4a16" and fp8:
+        raise ValueError("an int4 (w4a16) checkpoint cannot load into an fp8 target: use quantization='w4a16' or None")
+    if kind == "fp8" and w4a16:
+        raise ValueError("an fp8 checkpoint cannot load into a w4a16 target: use quantization='fp8' or None")
     index: dict[str, str] = {}
     for f in sorted(glob.glob(os.path.join(model_dir, "*.safetensors"))):
         with safe_open(f, "pt", "cpu") as sf:
@@ -405,12 +437,38 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
     if any(k.endswith("weight_scale_inv") for k in index):
         raise ValueError("block-scaled fp8 checkpoints (weight_scale_inv) are not supported: use per-channel or per-tensor scales")
     assert not (fp8 and tp > 1), "fp8 targets are single-rank"
+    assert not (w4a16 and tp > 1), "w4a16 targets are single-rank"
+    for k in index:
+        if k.endswith("weight_zero_point"):
+            raise ValueError(f"{k}: asymmetric int4 weights (zero points) are not supported")
+        if k.endswith("weight_g_idx"):
+            raise ValueError(f"{k}: int4 weights with activation reordering (g_idx) are not supported")
 
     def raw(name: str) -> torch.Tensor:
         with safe_open(index[name], "pt", "cpu") as sf:
             return sf.get_tensor(name)
 
+    def get_w4(name: str) -> W4Tensor:
+        base = name[:-len(".weight")]
+        if kind != "w4a16":
+            raise ValueError(f"{base}.weight_packed is int4 but config.json declares no pack-quantized int4 scheme")
+        packed, s = raw(base + ".weight_packed"), raw(base + ".weight_scale")
+        N, KW = packed.shape
+        if packed.dtype != torch.int32:
+            raise ValueError(f"{base}.weight_packed is {packed.dtype}: expected int32")
+        if base + ".weight_shape" in index:
+            shp = tuple(int(v) for v in raw(base + ".weight_shape").reshape(-1).tolist())
+            if shp != (N, KW * 8):
+                raise ValueError(f"{base}.weight_shape {shp} does not match weight_packed {tuple(packed.shape)}")
+        if tuple(s.shape) != (N, KW * 8 // 128):
+            raise ValueError(f"{base}.weight_scale has shape {tuple(s.shape)}: expected [{N}, {KW * 8 // 128}] (group size 128)")
+        if s.dtype not in (BF16, torch.float16, torch.float32):
+            raise ValueError(f"{base}.weight_scale is {s.dtype}: expected bf16, fp16 or fp32")
+        return W4Tensor(packed.contiguous(), s.to(BF16).contiguous())
+
     def get(name: str):
+        if name not in index and name.endswith(".weight") and name[:-len(".weight")] + ".weight_packed" in index:
+            return get_w4(name)
         t = raw(name)
         if t.dtype == FP8:
             if not ckpt_fp8:
@@ -439,8 +497,19 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
 
     for name, shape in param_shapes(cfg):
         srcs = packed_sources(name)
-        parts = [get(s) for s in srcs] if srcs is not None and name not in index else [get(name)]
-        if all(isinstance(p, tuple) for p in parts):
+        whole = name in index or name[:-len(".weight")] + ".weight_packed" in index
+        parts = [get(s) for s in srcs] if srcs is not None and not whole else [get(name)]
+        if all(isinstance(p, W4Tensor) for p in parts):
+            w = W4Tensor(torch.cat([p.packed for p in parts], dim=0), torch.cat([p.scale for p in parts], dim=0))
+            if not w4a16:
+                w = dequantize_w4a16(*w)
+            else:
+                assert (w.packed.shape[0], w.packed.shape[1] * 8) == tuple(shape), f"{name}: {tuple(w.packed.shape)} vs {shape}"
+                yield name, (W4Tensor(w.packed.to(out_device), w.scale.to(out_device)) if out_device is not None else w)
+                continue
+        elif any(isinstance(p, W4Tensor) for p in parts):
+            w = torch.cat([dequantize_w4a16(*p) if isinstance(p, W4Tensor) else p for p in parts], dim=0)
+        elif all(isinstance(p, tuple) for p in parts):
             w = (torch.cat([p[0] for p in parts], dim=0), torch.cat([p[1] for p in parts], dim=0))
         else:
             w = torch.cat([dequantize_fp8(*p) if isinstance(p, tuple) else p for p in parts], dim=0)
