@@ -76,7 +76,8 @@ class Config:
 
     # weight-only quantization of the TARGET's decoder linears (not in the reference): None = bf16, "fp8" = OCP e4m3fn codes with one
     # fp32 scale per output row (ssd_amd/quant.py, csrc/gemm_fp8.hip), "w4a16" = signed int4 codes with one bf16 scale per output row
-    # and 128-column group (csrc/gemm_w4a16.hip).  The draft, the embedding, the LM head, the norms, activations and the KV cache stay
+    # and 128-column group (csrc/gemm_w4a16.hip), "mxfp4" = OCP e2m1 codes with one e8m0 scale byte per output row and 32-column block
+    # (csrc/gemm_mxfp4.hip).  The draft, the embedding, the LM head, the norms, activations and the KV cache stay
     # bf16.
     quantization: str | None = None
 
@@ -90,8 +91,8 @@ class Config:
 
     def __post_init__(self):
         assert 1 <= self.num_gpus <= 8, "single node only (reference ssd/config.py:55)"
-        if self.quantization not in (None, "fp8", "w4a16"):
-            raise ValueError(f"quantization must be None, 'fp8' or 'w4a16', got {self.quantization!r}")
+        if self.quantization not in (None, "fp8", "w4a16", "mxfp4"):
+            raise ValueError(f"quantization must be None, 'fp8', 'w4a16' or 'mxfp4', got {self.quantization!r}")
         if self.quantization is not None and self.num_gpus > 1:
             raise ValueError(f"quantization={self.quantization!r} runs on one GPU only: tensor-parallel {self.quantization} shards are "
                              "not supported")

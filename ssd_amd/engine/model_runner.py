@@ -76,7 +76,7 @@ class ModelRunner:
                                            out_device=str(device))
         elif model_path is not None and W.has_safetensors(model_path):
             src = W.load_safetensors(model_cfg, model_path, tp_rank, tp_size, out_device=str(device), fp8=quantization == "fp8",
-                                   w4a16=quantization == "w4a16")
+                                   w4a16=quantization == "w4a16", mxfp4=quantization == "mxfp4")
         else:
             gd = gen_device or ("cuda" if model_cfg.hidden_size >= 1024 else "cpu")
             src = W.synthetic_weights(model_cfg, weights_seed, config.weights_std, tp_rank, tp_size, gen_device=gd,

@@ -1,0 +1,68 @@
+"""ctypes table and torch front end of the MXFP4 weight entry points (include/ssd_hip_mxfp4.h).
+
+Kept apart from ``lib.SIGNATURES`` (exactly ssd_hip.h + ssd_hip_tune.h), from ``quant_ops.QUANT_SIGNATURES`` (fp8) and from
+``w4_ops.W4_SIGNATURES`` (int4): these bind on the same libssdhip.so.  As in ops.py, nothing here computes in torch; the calls enqueue
+on the current stream and are hipGraph-capturable.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from .lib import load_library, SsdHipError
+from .ops import _p, _stream, _check, EPI_ROWS
+
+c_void_p, c_int = C.c_void_p, C.c_int
+
+# name -> argtypes, exactly include/ssd_hip_mxfp4.h
+MX4_SIGNATURES = {
+    "ssd_mx4_rows_to_frag": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "ssd_mx4_frag_to_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "ssd_mx4_dequant_frag": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "ssd_gemm_mxfp4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "ssd_gemm_mxfp4_cfg": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+}
+
+_MX4LIB = None
+
+
+def load_mx4_library():
+    global _MX4LIB
+    if _MX4LIB is not None:
+        return _MX4LIB
+    lib = load_library()
+    for name, args in MX4_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise SsdHipError(f"libssdhip.so does not export {name}") from e
+        fn.argtypes = args
+        fn.restype = c_int
+    _MX4LIB = lib
+    return lib
+
+
+def mx4_rows_to_frag(packed, scale, q_frag, s_frag, N: int, K: int, row_map=None):
+    """packed: uint8 [N, K/2]; scale: uint8 [N, K/32]; q_frag: N*K/2 bytes; s_frag: N*K/32 bytes; row_map: int32 [N] source row of
+    every destination row (None = identity)."""
+    _check(load_mx4_library().ssd_mx4_rows_to_frag(_p(packed), _p(scale), _p(q_frag), _p(s_frag), _p(row_map), N, K, _stream()),
+           "ssd_mx4_rows_to_frag")
+
+
+def mx4_frag_to_rows(q_frag, s_frag, packed, scale, N: int, K: int):
+    _check(load_mx4_library().ssd_mx4_frag_to_rows(_p(q_frag), _p(s_frag), _p(packed), _p(scale), N, K, _stream()),
+           "ssd_mx4_frag_to_rows")
+
+
+def mx4_dequant_frag(q_frag, s_frag, w_frag, N: int, K: int):
+    """bf16 frag [N, K] = 2^(b - 127) * e2m1(q) (exact) for the bf16 prefill GEMMs."""
+    _check(load_mx4_library().ssd_mx4_dequant_frag(_p(q_frag), _p(s_frag), _p(w_frag), N, K, _stream()), "ssd_mx4_dequant_frag")
+
+
+def gemm_mxfp4(x_frag, q_frag, s_frag, y, M: int, N: int, K: int, ldy: int, epilogue: int = EPI_ROWS, bias=None, cfg=None):
+    lib = load_mx4_library()
+    if cfg is None:
+        rc = lib.ssd_gemm_mxfp4(_p(x_frag), _p(q_frag), _p(s_frag), _p(bias), _p(y), M, N, K, ldy, epilogue, _stream())
+    else:
+        rc = lib.ssd_gemm_mxfp4_cfg(_p(x_frag), _p(q_frag), _p(s_frag), _p(bias), _p(y), M, N, K, ldy, epilogue, cfg[0], cfg[1],
+                                    _stream())
+    _check(rc, "ssd_gemm_mxfp4")

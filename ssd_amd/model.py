@@ -22,6 +22,7 @@ import torch.distributed as dist
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import quant_ops as Q
 from ssd_amd.hip import w4_ops as W4
+from ssd_amd.hip import mx4_ops as MX4
 from ssd_amd import quant
 from ssd_amd.model_config import ModelConfig
 
@@ -68,10 +69,13 @@ class HipDecoder:
         # -> GEMM.  Single rank only (Config refuses the rest).
         # quantization="w4a16": int4 codes + one bf16 scale per row and 128-column group (ssd_amd/quant.py), run on csrc/gemm_w4a16.hip,
         # with the same layer shape as fp8 (self.quantized turns the fused forms off for both).
-        assert quantization in (None, "fp8", "w4a16"), quantization
+        # quantization="mxfp4": e2m1 codes + one e8m0 scale byte per row and 32-column block (ssd_amd/quant.py), run on
+        # csrc/gemm_mxfp4.hip, same layer shape again.
+        assert quantization in (None, "fp8", "w4a16", "mxfp4"), quantization
         self.fp8 = quantization == "fp8"
         self.w4 = quantization == "w4a16"
-        self.quantized = self.fp8 or self.w4
+        self.mx4 = quantization == "mxfp4"
+        self.quantized = self.fp8 or self.w4 or self.mx4
         assert not self.quantized or (tp_size == 1 and not force_collectives and taps is None), \
             f"{quantization} targets are single-rank, without taps"
         self.tp_rank, self.tp_size, self.tp_group = tp_rank, tp_size, tp_group
@@ -91,6 +95,9 @@ class HipDecoder:
         if self.w4 and any(k % quant.W4_GROUP for k in (self.h, self.qn, self.I)):
             raise ValueError(f"quantization='w4a16' needs hidden_size, num_heads * head_dim and intermediate_size to be multiples of "
                              f"{quant.W4_GROUP} (the group size), got {self.h}, {self.qn}, {self.I}")
+        if self.mx4 and any(k % quant.MX4_GROUP for k in (self.h, self.qn, self.I)):
+            raise ValueError(f"quantization='mxfp4' needs hidden_size, num_heads * head_dim and intermediate_size to be multiples of "
+                             f"{quant.MX4_GROUP} (four 32-column blocks: one device unit), got {self.h}, {self.qn}, {self.I}")
         self.block_size, self.max_blocks = block_size, max_blocks
         self.max_tokens = max_tokens
         self.max_logit_rows = max_logit_rows or max_tokens
@@ -193,7 +200,8 @@ class HipDecoder:
         # the bf16 prefill GEMMs (compute-bound there, so the halved weight bytes buy nothing).  Allocated once: prefill hipGraphs
         # bake its pointer.
         # The same scratch serves w4a16 prompts longer than W4_DIRECT_MAX_T rows.
-        direct_max = self.W4_DIRECT_MAX_T if self.w4 else self.FP8_DIRECT_MAX_T
+        # ... and mxfp4 prompts longer than MX4_DIRECT_MAX_T rows.
+        direct_max = self.W4_DIRECT_MAX_T if self.w4 else self.MX4_DIRECT_MAX_T if self.mx4 else self.FP8_DIRECT_MAX_T
         self._deq = (z(max(n * k for n, k in pf_shapes[:4])) if self.quantized and max_tokens > direct_max else None)
         st = min(T, max_split_tokens)
         self.ws_o = z(st * self.nh * self.max_splits * self.hd, dtype=torch.float32)
@@ -224,8 +232,18 @@ class HipDecoder:
         (name, (q float8_e4m3fn [N, K], s fp32 [N])) from a pre-quantized checkpoint.  An fp8 decoder quantizes each bf16 linear
         as it arrives (never the whole model in both forms) and stores "<name>" = fp8 frag codes, "<name>_scale" = fp32 [N] in
         the packed row order.  Likewise a w4a16 decoder takes bf16 linears or quant.W4Tensor(packed, scale) from a pack-quantized
-        checkpoint and stores "<name>" = w4 frag codes, "<name>_scale" = bf16 w4 frag scales (include/ssd_hip_w4a16.h)."""
+        checkpoint and stores "<name>" = w4 frag codes, "<name>_scale" = bf16 w4 frag scales (include/ssd_hip_w4a16.h).  An mxfp4
+        decoder takes bf16 linears or quant.MX4Tensor(packed, scale) and stores "<name>" = mx4 frag codes, "<name>_scale" = mx4 frag
+        scale bytes (include/ssd_hip_mxfp4.h).  A bf16 decoder computes with the exact dequantized matrix of whatever it is handed;
+        a quantized decoder refuses tensors of another format."""
         for name, w in weight_iter:
+            if self.mx4 and quant.is_quantized_linear(name):
+                self._load_mx4(name, w)
+                continue
+            if isinstance(w, quant.MX4Tensor):
+                if self.quantized:
+                    raise ValueError(f"{name}: MXFP4 tensors cannot load into a {'fp8' if self.fp8 else 'w4a16'} decoder")
+                w = quant.dequantize_mxfp4(w.packed.to(self.device), w.scale.to(self.device))
             if self.fp8 and quant.is_quantized_linear(name):
                 self._load_fp8(name, w)
                 continue
@@ -296,6 +314,27 @@ class HipDecoder:
         self.w[name] = q_frag
         self.w[name + "_scale"] = s_frag
 
+    def _load_mx4(self, name: str, w) -> None:
+        if isinstance(w, tuple) and not isinstance(w, quant.MX4Tensor):
+            raise ValueError(f"{name}: fp8 / w4a16 tensors cannot load into an mxfp4 decoder")
+        if not isinstance(w, quant.MX4Tensor):
+            w = quant.quantize_mxfp4(w.to(self.device))
+        packed, s = w.packed.to(self.device).contiguous(), w.scale.to(self.device).contiguous()
+        N, K = packed.shape[0], packed.shape[1] * 2
+        assert packed.dtype == torch.uint8 and tuple(s.shape) == (N, K // quant.MX4_BLOCK), (name, packed.dtype, s.shape)
+        quant.check_mxfp4_scales(name, s)
+        if name.endswith("qkv_proj.weight"):
+            row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
+        elif name.endswith("gate_up_proj.weight"):
+            row_map = quant.gate_up_row_map(N).to(self.device)
+        else:
+            row_map = None
+        q_frag = torch.empty(N * K // 2, dtype=torch.uint8, device=self.device)
+        s_frag = torch.empty(N * K // quant.MX4_BLOCK, dtype=torch.uint8, device=self.device)
+        MX4.mx4_rows_to_frag(packed, s, q_frag, s_frag, N, K, row_map=row_map)
+        self.w[name] = q_frag
+        self.w[name + "_scale"] = s_frag
+
     def overwrite_weights(self, weight_iter) -> None:
         """New VALUES into the existing weight tensors (same names and shapes): captured hipGraphs keep pointing at the same memory, so a
         model can be given other weights without recapturing anything (bench.py: the independent-draft leg after the correlated one)."""
@@ -347,6 +386,8 @@ class HipDecoder:
     FP8_DIRECT_MAX_T = 128
     # w4a16 linears of up to this many rows run on the w4a16 GEMM itself; longer prompts dequantize into self._deq first
     W4_DIRECT_MAX_T = 128
+    # mxfp4 linears of up to this many rows run on the mxfp4 GEMM itself; longer prompts dequantize into self._deq first
+    MX4_DIRECT_MAX_T = 128
 
     @classmethod
     def _lm_eligible(cls, T: int) -> bool:
@@ -389,6 +430,12 @@ class HipDecoder:
                 W4.gemm_w4a16(xf, w, scale, y, T, N, K, ldy, epi, bias)
                 return
             W4.w4_dequant_frag(w, scale, self._deq, N, K)
+            w = self._deq
+        elif scale is not None and self.mx4:   # mxfp4 codes (w) + block scale bytes
+            if T <= self.MX4_DIRECT_MAX_T:
+                MX4.gemm_mxfp4(xf, w, scale, y, T, N, K, ldy, epi, bias)
+                return
+            MX4.mx4_dequant_frag(w, scale, self._deq, N, K)
             w = self._deq
         elif scale is not None:         # fp8 codes (w) + row scales
             if T <= self.FP8_DIRECT_MAX_T:

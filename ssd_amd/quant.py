@@ -1,5 +1,6 @@
 """Weight-only quantization of the decoder linears: FP8 (OCP e4m3fn) with one scale per row, W[N, K] ~= s[n] * q[n, k], and W4A16
-(int4 with one scale per row and 128-column group, further down).
+(int4 with one scale per row and 128-column group, further down), and MXFP4 (e2m1 codes with one e8m0 scale per row and 32-column
+block, at the end).
 
 The one-time load math is torch on the device; the re-tiling into the kernel layout is csrc/gemm_fp8.hip (ssd_fp8_rows_to_frag) and
 csrc/gemm_w4a16.hip (ssd_w4_rows_to_frag).  FP8:
@@ -113,3 +114,80 @@ def dequantize_w4a16(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     q = unpack_w4(packed).float()
     s = scale.float().repeat_interleave(W4_GROUP, dim=1)
     return (q * s).to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MXFP4 (OCP microscaling FP4): e2m1 codes (4 bits s e e m: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 for codes 0..7, sign in bit 3) with
+# one e8m0 scale byte b per output row and block of 32 consecutive columns, W = 2^(b - 127) * e2m1(q) (csrc/gemm_mxfp4.hip).
+# Supported scale bytes are 2 <= b <= 252: there 0.5 * 2^(b - 127) is a normal bf16 number and 6 * 2^(b - 127) is finite, so every
+# weight is exact in bf16 and the device never has to agree with the host about flushing or overflow.
+#
+# The host form: codes uint8 [N, K / 2], byte j of a row = column 2j in bits 0..3 and column 2j+1 in bits 4..7; scales uint8
+# [N, K / 32].  Widths must be multiples of MX4_GROUP = 128 (one 1 KiB device unit covers 16 rows x 128 columns = four blocks).
+# ---------------------------------------------------------------------------------------------------------------------
+MX4_BLOCK = 32
+MX4_GROUP = 128
+MX4_SCALE_MIN, MX4_SCALE_MAX = 2, 252
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)
+
+
+class MX4Tensor(NamedTuple):
+    """An MXFP4 decoder linear in the host form: packed uint8 [N, K / 2], scale uint8 [N, K / 32]."""
+    packed: torch.Tensor
+    scale: torch.Tensor
+
+
+def check_mxfp4_scales(name: str, scale: torch.Tensor) -> None:
+    """Refuses e8m0 scale bytes outside 2..252 (0, 1: weights that are bf16 subnormals; 253, 254: overflow; 255: NaN)."""
+    if scale.dtype != torch.uint8:
+        raise ValueError(f"{name}: MXFP4 scales are {scale.dtype}, expected uint8 (e8m0)")
+    lo, hi = int(scale.min()), int(scale.max())
+    if lo < MX4_SCALE_MIN or hi > MX4_SCALE_MAX:
+        bad = lo if lo < MX4_SCALE_MIN else hi
+        raise ValueError(f"{name}: MXFP4 scale byte {bad} is outside the supported range {MX4_SCALE_MIN}..{MX4_SCALE_MAX} "
+                         "(2^(b - 127) with every weight a normal, finite bf16 number; 255 is NaN)")
+
+
+def pack_mxfp4(codes: torch.Tensor) -> torch.Tensor:
+    """e2m1 codes [N, K] in 0..15 -> uint8 [N, K / 2] (column 2j in bits 0..3 of byte j, column 2j+1 in bits 4..7)."""
+    c = codes.to(torch.int32)
+    return (c[:, 0::2] | (c[:, 1::2] << 4)).to(torch.uint8)
+
+
+def unpack_mxfp4(packed: torch.Tensor) -> torch.Tensor:
+    """uint8 [N, K / 2] -> e2m1 codes uint8 [N, K] in 0..15."""
+    p = packed.to(torch.int32)
+    return torch.stack((p & 0xF, p >> 4), dim=-1).reshape(packed.shape[0], -1).to(torch.uint8)
+
+
+def quantize_mxfp4(w: torch.Tensor) -> MX4Tensor:
+    """[N, K] bf16 (K % 128 == 0) -> MX4Tensor(packed uint8 [N, K / 2], scale uint8 [N, K / 32]), on w's device: the OCP MX v1.0
+    conversion, in fp32.  Per block of 32 columns
+
+        amax = max |w|
+        b = max(floor(log2(amax)) - 2 + 127, 2)         (the floor is the fp32 exponent field; an all-zero block gets b = 127, q = 0;
+                                                         finite bf16 inputs never exceed 252)
+        q = e2m1(w / 2^(b - 127))                       (round to nearest, ties to the even code, saturating at +-6)
+
+    so amax / 2^(b - 127) lies in [4, 8) unless the clamp at 2 took hold.  The ties and the saturation, on magnitudes: 0.25 -> 0,
+    0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4, anything above 6 -> 6.  The sign bit is that of w (a negative value
+    that rounds to zero keeps it: code 8 = -0; -0.0 itself gives code 0)."""
+    N, K = w.shape
+    assert K % MX4_GROUP == 0, f"MXFP4 needs K % {MX4_GROUP} == 0, got {K}"
+    wf = w.float().reshape(N, K // MX4_BLOCK, MX4_BLOCK)
+    amax = wf.abs().amax(-1)
+    e = (amax.view(torch.int32) >> 23) & 0xFF
+    b = torch.where(amax == 0, torch.full_like(e, 127), (e - 2).clamp_min(MX4_SCALE_MIN))
+    a = (wf / (b << 23).view(torch.float32)[..., None]).abs()
+    q = (a > 0.25).to(torch.int32) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0)
+    q = q | ((wf < 0).to(torch.int32) << 3)
+    return MX4Tensor(pack_mxfp4(q.reshape(N, K)), b.to(torch.uint8))
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K] = 2^(b - 127) * e2m1(q), exact for 2 <= b <= 252: the weights an MXFP4 target computes with (oracles, a bf16 decoder
+    given MXFP4 tensors)."""
+    lut = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=packed.device)
+    v = lut[unpack_mxfp4(packed).long()]
+    s = (scale.to(torch.int32) << 23).view(torch.float32).repeat_interleave(MX4_BLOCK, dim=1)
+    return (v * s).to(torch.bfloat16)

@@ -387,13 +387,43 @@ def checkpoint_quantization(model_dir: str) -> str | None:
         if wq.get("type") == "int" and wq.get("num_bits") == 4:
             kinds.add(_w4a16_scheme(gname, wq, qc.get("format")))
             continue
+        if wq.get("type") == "float" and wq.get("num_bits") == 4:
+            kinds.add(_mxfp4_scheme(gname, wq, qc.get("format")))
+            continue
         if wq.get("type") != "float" or wq.get("num_bits") != 8 or wq.get("strategy") not in ("channel", "tensor"):
             raise ValueError(f"unsupported compressed-tensors weight scheme in {gname}: {wq} (supported: type float, num_bits 8, "
-                             "strategy channel or tensor; or type int, num_bits 4, strategy group, group_size 128)")
+                             "strategy channel or tensor; or type int, num_bits 4, strategy group, group_size 128; or type float, num_bits 4, "
+                             "strategy group, group_size 32)")
         kinds.add("fp8")
     if len(kinds) > 1:
         raise ValueError(f"compressed-tensors checkpoint mixes weight schemes {sorted(kinds)}")
     return kinds.pop()
+
+
+# compressed-tensors names of an MXFP4 checkpoint, kept in one place: they are written from memory of the format and have not been
+# checked against a published checkpoint ("MXFP4 weight-only targets")
+MXFP4_FORMAT = "mxfp4-pack-quantized"
+MXFP4_PACKED_SUFFIX, MXFP4_SCALE_SUFFIX, FP4_GLOBAL_SCALE_SUFFIX = ".weight_packed", ".weight_scale", ".weight_global_scale"
+
+
+def _mxfp4_scheme(gname: str, wq: dict, fmt) -> str:
+    """The float-4 scheme an MXFP4 target runs: e2m1 codes, symmetric, one e8m0 (uint8) scale per 32-column group, mxfp4-pack-quantized.
+    NVFP4 (group size 16, fp8-typed scales, a global scale) is refused here by name."""
+    if wq.get("group_size") == 16 or fmt == "nvfp4-pack-quantized":
+        raise ValueError(f"unsupported float-4 scheme in {gname}: group_size {wq.get('group_size')!r} / format {fmt!r} is NVFP4; only "
+                         f"MXFP4 (format {MXFP4_FORMAT}, group_size 32, e8m0 scales) can be loaded")
+    if fmt != MXFP4_FORMAT:
+        raise ValueError(f"unsupported compressed-tensors format {fmt!r} for float-4 weights in {gname}: only {MXFP4_FORMAT}")
+    if wq.get("strategy") != "group":
+        raise ValueError(f"unsupported float-4 weight strategy {wq.get('strategy')!r} in {gname}: only strategy group")
+    if wq.get("group_size") != 32:
+        raise ValueError(f"unsupported float-4 group_size {wq.get('group_size')!r} in {gname}: only 32 (MXFP4)")
+    if wq.get("symmetric") is not True:
+        raise ValueError(f"asymmetric float-4 weights in {gname} are not supported: symmetric only")
+    sd = wq.get("scale_dtype")
+    if sd is not None and "uint8" not in str(sd) and "e8m0" not in str(sd):
+        raise ValueError(f"unsupported float-4 scale_dtype {sd!r} in {gname}: fp8-typed scales are NVFP4; MXFP4 scales are e8m0 (uint8)")
+    return "mxfp4"
 
 
 def _w4a16_scheme(gname: str, wq: dict, fmt) -> str:
@@ -412,19 +442,28 @@ def _w4a16_scheme(gname: str, wq: dict, fmt) -> str:
 
 
 def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 1,
-                     out_device: str | None = None, fp8: bool = False, w4a16: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
+                     out_device: str | None = None, fp8: bool = False, w4a16: bool = False,
+                     mxfp4: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
     """Yields (name, bf16 tensor).  From a compressed-tensors fp8 checkpoint (checkpoint_quantization), a quantized decoder linear
     comes as (name, (q float8_e4m3fn [N, K], s fp32 [N])) when ``fp8`` (the consumer is an fp8 target: no re-quantization) and as
     bf16(s * q) otherwise.  Per-tensor scales of the packed q / k / v and gate / up are expanded to one per row before the packing;
     input_scale tensors (activation quantization) are ignored; unquantized tensors (e.g. the LM head) load as bf16.
     From a pack-quantized int4 checkpoint, a quantized linear comes as (name, W4Tensor(packed int32 [N, K/8], scale bf16 [N, K/128]))
     when ``w4a16`` (codes and bf16 scales bit for bit; fp16 / fp32 scales are rounded to bf16 once) and as bf16(s * q), sharded as
-    usual, otherwise.  A W4A16 checkpoint into an fp8 target and an fp8 one into a W4A16 target are refused."""
+    usual, otherwise.  A W4A16 checkpoint into an fp8 target and an fp8 one into a W4A16 target are refused.
+    From an MXFP4 checkpoint, a quantized linear comes as (name, MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32])) when
+    ``mxfp4`` (codes and scale bytes bit for bit; scale bytes outside 2..252 are refused) and as the exact bf16 matrix
+    2^(b - 127) * e2m1(q), sharded as usual, otherwise.  MXFP4 checkpoints into fp8 / w4a16 targets and the reverse are refused."""
     from safetensors import safe_open
-    from ssd_amd.quant import FP8, dequantize_fp8, W4Tensor, dequantize_w4a16
-    assert not (fp8 and w4a16)
+    from ssd_amd.quant import FP8, dequantize_fp8, W4Tensor, dequantize_w4a16, MX4Tensor, dequantize_mxfp4, check_mxfp4_scales
+    assert fp8 + w4a16 + mxfp4 <= 1
     kind = checkpoint_quantization(model_dir)
     ckpt_fp8 = kind == "fp8"
+    if kind == "mxfp4" and (fp8 or w4a16):
+        raise ValueError(f"an mxfp4 checkpoint cannot load into {'an fp8' if fp8 else 'a w4a16'} target: use quantization='mxfp4' or None")
+    if kind in ("fp8", "w4a16") and mxfp4:
+        raise ValueError(f"{'an fp8' if kind == 'fp8' else 'an int4 (w4a16)'} checkpoint cannot load into an mxfp4 target: use "
+                         f"quantization={kind!r} or None")
     if kind == "w4a16" and fp8:
         raise ValueError("an int4 (w4a16) checkpoint cannot load into an fp8 target: use quantization='w4a16' or None")
     if kind == "fp8" and w4a16:
@@ -438,6 +477,10 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         raise ValueError("block-scaled fp8 checkpoints (weight_scale_inv) are not supported: use per-channel or per-tensor scales")
     assert not (fp8 and tp > 1), "fp8 targets are single-rank"
     assert not (w4a16 and tp > 1), "w4a16 targets are single-rank"
+    assert not (mxfp4 and tp > 1), "mxfp4 targets are single-rank"
+    for k in index:
+        if k.endswith(FP4_GLOBAL_SCALE_SUFFIX):
+            raise ValueError(f"{k}: float-4 weights with a global scale tensor (NVFP4) are not supported; only MXFP4")
     for k in index:
         if k.endswith("weight_zero_point"):
             raise ValueError(f"{k}: asymmetric int4 weights (zero points) are not supported")
@@ -466,9 +509,22 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
             raise ValueError(f"{base}.weight_scale is {s.dtype}: expected bf16, fp16 or fp32")
         return W4Tensor(packed.contiguous(), s.to(BF16).contiguous())
 
+    def get_mx4(name: str) -> MX4Tensor:
+        base = name[:-len(".weight")]
+        packed, s = raw(base + MXFP4_PACKED_SUFFIX), raw(base + MXFP4_SCALE_SUFFIX)
+        if packed.dtype != torch.uint8:
+            raise ValueError(f"{base}{MXFP4_PACKED_SUFFIX} is {packed.dtype}: expected uint8 (two e2m1 codes per byte)")
+        N, KB = packed.shape
+        if s.dtype != torch.uint8:
+            raise ValueError(f"{base}{MXFP4_SCALE_SUFFIX} is {s.dtype}: expected uint8 (e8m0); fp8-typed scales are NVFP4")
+        if tuple(s.shape) != (N, KB * 2 // 32):
+            raise ValueError(f"{base}{MXFP4_SCALE_SUFFIX} has shape {tuple(s.shape)}: expected [{N}, {KB * 2 // 32}] (group size 32)")
+        check_mxfp4_scales(base + MXFP4_SCALE_SUFFIX, s)
+        return MX4Tensor(packed.contiguous(), s.contiguous())
+
     def get(name: str):
         if name not in index and name.endswith(".weight") and name[:-len(".weight")] + ".weight_packed" in index:
-            return get_w4(name)
+            return get_mx4(name) if kind == "mxfp4" else get_w4(name)
         t = raw(name)
         if t.dtype == FP8:
             if not ckpt_fp8:
@@ -499,7 +555,16 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         srcs = packed_sources(name)
         whole = name in index or name[:-len(".weight")] + ".weight_packed" in index
         parts = [get(s) for s in srcs] if srcs is not None and not whole else [get(name)]
-        if all(isinstance(p, W4Tensor) for p in parts):
+        if all(isinstance(p, MX4Tensor) for p in parts):
+            w = MX4Tensor(torch.cat([p.packed for p in parts], dim=0), torch.cat([p.scale for p in parts], dim=0))
+            if mxfp4:
+                assert (w.packed.shape[0], w.packed.shape[1] * 2) == tuple(shape), f"{name}: {tuple(w.packed.shape)} vs {shape}"
+                yield name, (MX4Tensor(w.packed.to(out_device), w.scale.to(out_device)) if out_device is not None else w)
+                continue
+            w = dequantize_mxfp4(*w)
+        elif any(isinstance(p, MX4Tensor) for p in parts):
+            w = torch.cat([dequantize_mxfp4(*p) if isinstance(p, MX4Tensor) else p for p in parts], dim=0)
+        elif all(isinstance(p, W4Tensor) for p in parts):
             w = W4Tensor(torch.cat([p.packed for p in parts], dim=0), torch.cat([p.scale for p in parts], dim=0))
             if not w4a16:
                 w = dequantize_w4a16(*w)
