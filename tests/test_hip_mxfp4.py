@@ -153,18 +153,8 @@ def _check_rows(dev, M, N, K, bias_on, what, seed=0, cfg=None):
     assert_within_ulp(y, want, what)
 
 
-def _check_silu(dev, M, I, K, what, seed=0):
-    from ssd_amd.quant import gate_up_row_map
-    from ssd_amd.hip import mx4_ops as MX4
-    from ssd_amd.hip import ops as H
-    packed, s = _codes(2 * I, K, dev, seed)
-    qf, sf = _frag(packed, s, 2 * I, K, dev, gate_up_row_map(2 * I).to(dev))
-    x, xf = _x(M, K, dev, seed + 1)
-    yf = torch.zeros(H.frag_numel(M, I), dtype=BF, device=dev)
-    MX4.gemm_mxfp4(xf, qf, sf, yf, M, 2 * I, K, 0, epilogue=H.EPI_SILU_FRAG)
-    y = torch.empty(M, I, dtype=BF, device=dev)
-    H.frag_to_rows(yf, y, M, I)
-    yg = x.double() @ _exact(packed, s).T
+def assert_silu_within_bar(y: torch.Tensor, yg: torch.Tensor, I: int, what: str):
+    """The SILU_FRAG bar: y bf16 [M, I] from the kernel against yg = the f64 [M, 2I] (gate | up) sums before any rounding."""
     g, u = yg[:, :I].to(BF).double(), yg[:, I:].to(BF).double()
     sg = torch.sigmoid(g)
     want = g * sg * u
@@ -177,6 +167,20 @@ def _check_silu(dev, M, I, K, what, seed=0):
     bad = d > tol
     print(f"{what}: worst {(d / tol).max().item():.2f} x tol")
     assert not bool(bad.any()), f"{what}: {int(bad.sum())} outputs beyond the bar, worst {(d / tol).max().item():.2f} x tol"
+
+
+def _check_silu(dev, M, I, K, what, seed=0):
+    from ssd_amd.quant import gate_up_row_map
+    from ssd_amd.hip import mx4_ops as MX4
+    from ssd_amd.hip import ops as H
+    packed, s = _codes(2 * I, K, dev, seed)
+    qf, sf = _frag(packed, s, 2 * I, K, dev, gate_up_row_map(2 * I).to(dev))
+    x, xf = _x(M, K, dev, seed + 1)
+    yf = torch.zeros(H.frag_numel(M, I), dtype=BF, device=dev)
+    MX4.gemm_mxfp4(xf, qf, sf, yf, M, 2 * I, K, 0, epilogue=H.EPI_SILU_FRAG)
+    y = torch.empty(M, I, dtype=BF, device=dev)
+    H.frag_to_rows(yf, y, M, I)
+    assert_silu_within_bar(y, x.double() @ _exact(packed, s).T, I, what)
 
 
 @pytest.mark.parametrize("M", [1, 7, 8, 24, 32, 64, 128])
