@@ -189,7 +189,8 @@ def ktable(args):
             print(f"{kind},{N},{K},{dtype},{names.pop()},{len(d)},{avg:.2f},{min(d):.2f},{nbytes},{nbytes / (avg * 1e-6) / HBM:.4f}")
 
 
-def step(args):
+def step(args, engine_kw=None):
+    """engine_kw: further LLMEngine keywords (w4zp_probe.py passes w4_zero_point)."""
     import bench
     from ssd_amd.engine.llm_engine import LLMEngine, METRICS
     from ssd_amd.sampling_params import SamplingParams
@@ -205,7 +206,7 @@ def step(args):
               inprocess_draft=True, num_draft_gpus=1)
     quant = None if args.quant == "none" else args.quant
     t0 = time.perf_counter()
-    engine = LLMEngine(tname, quantization=quant, **kw)
+    engine = LLMEngine(tname, quantization=quant, **(engine_kw or {}), **kw)
     print(json.dumps({"probe": "engine_init", "quant": args.quant, "s": round(time.perf_counter() - t0, 1),
                       "target_weight_bytes": engine.model_runner.model.weight_bytes()}), flush=True)
     dev = torch.device("cuda", 0)

@@ -80,6 +80,10 @@ class Config:
     # (csrc/gemm_mxfp4.hip).  The draft, the embedding, the LM head, the norms, activations and the KV cache stay
     # bf16.
     quantization: str | None = None
+    # quantization="w4a16" only: quantize bf16 / synthetic weights on load with the min/max zero-point quantizer
+    # (quant.quantize_w4a16_zp: unsigned codes, one 4-bit zero point per row and group, run on the zero-point GEMM) instead of the
+    # symmetric one.  Checkpoints that carry zero points (AutoAWQ, asymmetric GPTQ) run on that GEMM whatever this says.
+    w4_zero_point: bool = False
 
     @property
     def max_blocks(self) -> int:
@@ -93,6 +97,8 @@ class Config:
         assert 1 <= self.num_gpus <= 8, "single node only (reference ssd/config.py:55)"
         if self.quantization not in (None, "fp8", "w4a16", "mxfp4"):
             raise ValueError(f"quantization must be None, 'fp8', 'w4a16' or 'mxfp4', got {self.quantization!r}")
+        if self.w4_zero_point and self.quantization != "w4a16":
+            raise ValueError(f"w4_zero_point=True needs quantization='w4a16', got quantization={self.quantization!r}")
         if self.quantization is not None and self.num_gpus > 1:
             raise ValueError(f"quantization={self.quantization!r} runs on one GPU only: tensor-parallel {self.quantization} shards are "
                              "not supported")

@@ -19,6 +19,7 @@ constexpr int SSD_MAX_DEVICES = 16;  // per-device host-side caches (function at
 #include "ssd_hip_tune.h"
 #include "ssd_hip_quant.h"
 #include "ssd_hip_w4a16.h"
+#include "ssd_hip_w4zp.h"
 #include "ssd_hip_mxfp4.h"
 
 __device__ __forceinline__ float bf2f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }

@@ -22,6 +22,7 @@ import torch.distributed as dist
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import quant_ops as Q
 from ssd_amd.hip import w4_ops as W4
+from ssd_amd.hip import w4zp_ops as W4Z
 from ssd_amd.hip import mx4_ops as MX4
 from ssd_amd import quant
 from ssd_amd.model_config import ModelConfig
@@ -61,14 +62,17 @@ class HipDecoder:
     def __init__(self, cfg: ModelConfig, *, max_tokens: int, max_seqs: int, max_blocks: int, block_size: int,
                  max_model_len: int, device: torch.device, tp_rank: int = 0, tp_size: int = 1, tp_group=None,
                  max_logit_rows: int | None = None, max_split_tokens: int = 256, force_collectives: bool = False,
-                 taps: list[int] | None = None, quantization: str | None = None):
+                 taps: list[int] | None = None, quantization: str | None = None, w4_zero_point: bool = False):
         self.cfg, self.device = cfg, device
         # quantization="fp8": the decoder linears are e4m3 codes + per-row fp32 scales (ssd_amd/quant.py) and run on csrc/gemm_fp8.hip;
         # every bf16-only fused form (norm prologues, the QKV+RoPE epilogue, split-K slabs, attention + o_proj, the resident chain /
         # tree segments, prefill partials) is off, so a layer is norm -> GEMM -> RoPE / KV store -> attention -> GEMM -> norm -> GEMM
         # -> GEMM.  Single rank only (Config refuses the rest).
         # quantization="w4a16": int4 codes + one bf16 scale per row and 128-column group (ssd_amd/quant.py), run on csrc/gemm_w4a16.hip,
-        # with the same layer shape as fp8 (self.quantized turns the fused forms off for both).
+        # with the same layer shape as fp8 (self.quantized turns the fused forms off for both).  A linear may carry one 4-bit zero
+        # point per row and group as well (quant.W4ZTensor from an AWQ / GPTQ checkpoint, or w4_zero_point=True for the on-load
+        # quantizer): it keeps a "<name>_zero" table and runs on the zero-point instantiations of the same kernel; symmetric and
+        # zero-point linears mix freely in one model.
         # quantization="mxfp4": e2m1 codes + one e8m0 scale byte per row and 32-column block (ssd_amd/quant.py), run on
         # csrc/gemm_mxfp4.hip, same layer shape again.
         assert quantization in (None, "fp8", "w4a16", "mxfp4"), quantization
@@ -76,6 +80,9 @@ class HipDecoder:
         self.w4 = quantization == "w4a16"
         self.mx4 = quantization == "mxfp4"
         self.quantized = self.fp8 or self.w4 or self.mx4
+        if w4_zero_point and not self.w4:
+            raise ValueError(f"w4_zero_point=True needs quantization='w4a16', got {quantization!r}")
+        self.w4_zero_point = w4_zero_point
         assert not self.quantized or (tp_size == 1 and not force_collectives and taps is None), \
             f"{quantization} targets are single-rank, without taps"
         self.tp_rank, self.tp_size, self.tp_group = tp_rank, tp_size, tp_group
@@ -234,9 +241,14 @@ class HipDecoder:
         the packed row order.  Likewise a w4a16 decoder takes bf16 linears or quant.W4Tensor(packed, scale) from a pack-quantized
         checkpoint and stores "<name>" = w4 frag codes, "<name>_scale" = bf16 w4 frag scales (include/ssd_hip_w4a16.h).  An mxfp4
         decoder takes bf16 linears or quant.MX4Tensor(packed, scale) and stores "<name>" = mx4 frag codes, "<name>_scale" = mx4 frag
-        scale bytes (include/ssd_hip_mxfp4.h).  A bf16 decoder computes with the exact dequantized matrix of whatever it is handed;
-        a quantized decoder refuses tensors of another format."""
+        scale bytes (include/ssd_hip_mxfp4.h).  A w4a16 decoder also takes quant.W4ZTensor(packed, scale, zero) and then stores
+        "<name>_zero" = the zero-point table (include/ssd_hip_w4zp.h) next to the other two.  A bf16 decoder computes with the exact
+        dequantized matrix of whatever it is handed; a quantized decoder refuses tensors of another format."""
         for name, w in weight_iter:
+            if isinstance(w, quant.W4ZTensor) and not self.w4:
+                if self.quantized:
+                    raise ValueError(f"{name}: zero-point int4 tensors cannot load into {'an fp8' if self.fp8 else 'an mxfp4'} decoder")
+                w = quant.dequantize_w4zp(w.packed.to(self.device), w.scale.to(self.device), w.zero.to(self.device))
             if self.mx4 and quant.is_quantized_linear(name):
                 self._load_mx4(name, w)
                 continue
@@ -297,11 +309,15 @@ class HipDecoder:
         self.w[name + "_scale"] = s
 
     def _load_w4(self, name: str, w) -> None:
-        if not isinstance(w, quant.W4Tensor):
-            w = quant.quantize_w4a16(w.to(self.device))
+        if not isinstance(w, (quant.W4Tensor, quant.W4ZTensor)):
+            w = quant.quantize_w4a16_zp(w.to(self.device)) if self.w4_zero_point else quant.quantize_w4a16(w.to(self.device))
         packed, s = w.packed.to(self.device).contiguous(), w.scale.to(self.device).to(BF16).contiguous()
         N, K = packed.shape[0], packed.shape[1] * 8
         assert packed.dtype == torch.int32 and tuple(s.shape) == (N, K // quant.W4_GROUP), (name, packed.dtype, s.shape)
+        zero = None
+        if isinstance(w, quant.W4ZTensor):
+            zero = w.zero.to(self.device).contiguous()
+            assert zero.dtype == torch.uint8 and zero.shape == s.shape and int(zero.max()) <= 15, (name, zero.dtype, zero.shape)
         if name.endswith("qkv_proj.weight"):
             row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
         elif name.endswith("gate_up_proj.weight"):
@@ -310,7 +326,12 @@ class HipDecoder:
             row_map = None
         q_frag = torch.empty(N * K // 2, dtype=torch.uint8, device=self.device)
         s_frag = torch.empty(N * K // quant.W4_GROUP, dtype=BF16, device=self.device)
-        W4.w4_rows_to_frag(packed, s, q_frag, s_frag, N, K, row_map=row_map)
+        if zero is not None:
+            z_frag = torch.empty(N * K // quant.W4_GROUP, dtype=torch.uint8, device=self.device)
+            W4Z.w4zp_rows_to_frag(packed, s, zero, q_frag, s_frag, z_frag, N, K, row_map=row_map)
+            self.w[name + "_zero"] = z_frag
+        else:
+            W4.w4_rows_to_frag(packed, s, q_frag, s_frag, N, K, row_map=row_map)
         self.w[name] = q_frag
         self.w[name + "_scale"] = s_frag
 
@@ -424,8 +445,14 @@ class HipDecoder:
         H.gemm_pf(xf, w, None, T, N, K, N, self._ws_pf, epilogue=H.PF_EPI_PARTIALS)
         return S
 
-    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None):
-        if scale is not None and self.w4:   # w4a16 codes (w) + group scales
+    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None, zero=None):
+        if scale is not None and self.w4 and zero is not None:   # w4a16 codes (w) + group scales + group zero points
+            if T <= self.W4_DIRECT_MAX_T:
+                W4Z.gemm_w4a16_zp(xf, w, scale, zero, y, T, N, K, ldy, epi, bias)
+                return
+            W4Z.w4zp_dequant_frag(w, scale, zero, self._deq, N, K)
+            w = self._deq
+        elif scale is not None and self.w4:   # w4a16 codes (w) + group scales
             if T <= self.W4_DIRECT_MAX_T:
                 W4.gemm_w4a16(xf, w, scale, y, T, N, K, ldy, epi, bias)
                 return
@@ -678,7 +705,8 @@ class HipDecoder:
                                   k_norm_w=w.get(p + "self_attn.k_norm.weight"), eps=cfg.rms_norm_eps, qkv_perm=1)
         else:
             self._gemm(xf, self.h, w[p + "self_attn.qkv_proj.weight"], self.qkv_n, self.buf_qkv, T, self.qkv_n,
-                       bias=w.get(p + "self_attn.qkv_proj.bias"), scale=w.get(p + "self_attn.qkv_proj.weight_scale"))
+                       bias=w.get(p + "self_attn.qkv_proj.bias"), scale=w.get(p + "self_attn.qkv_proj.weight_scale"),
+                       zero=w.get(p + "self_attn.qkv_proj.weight_zero"))
             if gemm_only:
                 return
             H.rope_store_kv(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
@@ -695,7 +723,8 @@ class HipDecoder:
             S, wv = self._parts("o", T)
             H.gemm_parts(self.buf_af, w, T, self.h, self.qn, parts=self.buf_parts_o, splits=S, waves=wv)
         else:
-            self._gemm(self.buf_af, self.qn, w, self.h, self.buf_h, T, self.h, scale=ws)
+            self._gemm(self.buf_af, self.qn, w, self.h, self.buf_h, T, self.h, scale=ws,
+                       zero=self.w.get(f"model.layers.{li}.self_attn.o_proj.weight_zero"))
         return 0
 
     def launch_gate_up(self, li: int, T: int, gemm_only: bool = False, pre_normed: bool = False, parts: bool | None = None,
@@ -723,7 +752,7 @@ class HipDecoder:
                     H.rmsnorm(self.buf_h, w[p + "post_attention_layernorm.weight"], cfg.rms_norm_eps, T, self.h,
                               res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
             self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG,
-                       scale=w.get(p + "mlp.gate_up_proj.weight_scale"))
+                       scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"))
 
     def launch_down(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> int:
         w = self.w[f"model.layers.{li}.mlp.down_proj.weight"]
@@ -734,7 +763,8 @@ class HipDecoder:
             S, wv = self._parts("d", T)
             H.gemm_parts(self.buf_actf, w, T, self.h, self.I, parts=self.buf_parts_d, splits=S, waves=wv)
         else:
-            self._gemm(self.buf_actf, self.I, w, self.h, self.buf_h, T, self.h, scale=ws)
+            self._gemm(self.buf_actf, self.I, w, self.h, self.buf_h, T, self.h, scale=ws,
+                       zero=self.w.get(f"model.layers.{li}.mlp.down_proj.weight_zero"))
         return 0
 
     def forward(self, input_ids: torch.Tensor, positions: torch.Tensor, T: int, meta: AttnMeta) -> None:

@@ -117,6 +117,73 @@ def dequantize_w4a16(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# W4A16 with zero points (include/ssd_hip_w4zp.h): unsigned codes u in [0, 15], one bf16 scale s and one integer zero point z in
+# [0, 15] per output row and 128-column group, W = s[n, k // 128] * (u[n, k] - z[n, k // 128]): the form of AWQ and asymmetric GPTQ
+# checkpoints.  The symmetric W4Tensor above is the special case z = 8 (its nibble is u = q + 8), and the packing is pack_w4's with
+# the nibble u itself.  The min/max quantizer, round to nearest even, fp32 on the tensor's device, per group:
+#
+#     lo = min w, hi = max w, range = hi - lo          (an all-equal group, range == 0: range = 15 * |lo|, see below)
+#     s = bf16_rne(max(range, W4ZP_TINY) / 15)
+#     z = clamp(rne(-lo / s), 0, 15)
+#     u = clamp(rne(w / s) + z, 0, 15)
+#
+# An all-equal group of value c takes the range 15 |c|, so s = |c| exactly (c is bf16) and the group is reproduced exactly:
+# c > 0 gives z = 0 (rne(-1) clamped), u = 1; c < 0 gives z = 1, u = 0; c = 0 gives s = W4ZP_TINY / 15, z = 0, u = 0.  (With the
+# plain range 0 the scale would be the tiny floor and z, u would both saturate; with range |c| the scale bf16(|c| / 15) is
+# inexact and 15 s != c.)  W4ZP_TINY = 15 * 2^-126 keeps s a normal, non-zero bf16 number.
+# ---------------------------------------------------------------------------------------------------------------------
+W4ZP_TINY = 15.0 * 2.0 ** -126
+
+
+class W4ZTensor(NamedTuple):
+    """A W4A16 decoder linear with zero points in the host row form: packed int32 [N, K / 8] (column 8j+i in bits 4i .. 4i+3 of word
+    j, the nibble is u), scale bf16 [N, K / 128], zero uint8 [N, K / 128] in 0..15."""
+    packed: torch.Tensor
+    scale: torch.Tensor
+    zero: torch.Tensor
+
+
+def pack_w4u(u: torch.Tensor) -> torch.Tensor:
+    """unsigned codes [N, K] in [0, 15] -> int32 [N, K / 8] (pack_w4's layout with the nibble u)."""
+    return pack_w4(u.to(torch.int64) - 8)
+
+
+def unpack_w4u(packed: torch.Tensor) -> torch.Tensor:
+    """int32 [N, K / 8] -> uint8 codes [N, K] in [0, 15]."""
+    return (unpack_w4(packed).to(torch.int16) + 8).to(torch.uint8)
+
+
+def quantize_w4a16_zp(w: torch.Tensor) -> W4ZTensor:
+    """[N, K] bf16 (K % 128 == 0) -> W4ZTensor, on w's device: the min/max quantizer described above."""
+    N, K = w.shape
+    assert K % W4_GROUP == 0, f"W4A16 needs K % {W4_GROUP} == 0, got {K}"
+    wf = w.float().reshape(N, K // W4_GROUP, W4_GROUP)
+    lo, hi = wf.amin(-1), wf.amax(-1)
+    rng = hi - lo
+    rng = torch.where(rng == 0, 15.0 * lo.abs(), rng)
+    s = (rng.clamp_min(W4ZP_TINY) / 15.0).to(torch.bfloat16)
+    sf = s.float()
+    z = torch.round(-lo / sf).clamp(0, 15)
+    u = (torch.round(wf / sf[..., None]) + z[..., None]).clamp(0, 15).reshape(N, K)
+    return W4ZTensor(pack_w4u(u), s, z.to(torch.uint8))
+
+
+def dequantize_w4zp(packed: torch.Tensor, scale: torch.Tensor, zero: torch.Tensor) -> torch.Tensor:
+    """bf16(s * (u - z)), the product in fp32: the weights a zero-point W4A16 linear computes with (oracles, a bf16 decoder given
+    such tensors)."""
+    u = unpack_w4u(packed).float()
+    s = scale.float().repeat_interleave(W4_GROUP, dim=1)
+    z = zero.float().repeat_interleave(W4_GROUP, dim=1)
+    return (s * (u - z)).to(torch.bfloat16)
+
+
+def w4z_as_symmetric(w: W4ZTensor) -> "W4Tensor | W4ZTensor":
+    """A linear whose zero points all equal 8 is the symmetric format bit for bit: hand it on as a W4Tensor (no zero table, the
+    symmetric kernel)."""
+    return W4Tensor(w.packed, w.scale) if bool((w.zero == 8).all()) else w
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # MXFP4 (OCP microscaling FP4): e2m1 codes (4 bits s e e m: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 for codes 0..7, sign in bit 3) with
 # one e8m0 scale byte b per output row and block of 32 consecutive columns, W = 2^(b - 127) * e2m1(q) (csrc/gemm_mxfp4.hip).
 # Supported scale bytes are 2 <= b <= 252: there 0.5 * 2^(b - 127) is a normal bf16 number and 6 * 2^(b - 127) is finite, so every

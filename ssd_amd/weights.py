@@ -362,22 +362,80 @@ def load_eagle_safetensors(cfg: ModelConfig, model_dir: str, target_dir: str | N
         yield name, (w.to(out_device) if out_device is not None else w)
 
 
-def checkpoint_quantization(model_dir: str) -> str | None:
-    """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales, "w4a16" for a
-    pack-quantized one with symmetric int4 weights in groups of 128 columns (config.json quantization_config), None for an
-    unquantized one; every other quantization format is refused here, before any tensor is read."""
+def _quantization_config(model_dir: str) -> dict | None:
     import json
     path = os.path.join(model_dir, "config.json")
     if not os.path.exists(path):
         return None
     with open(path) as f:
-        qc = json.load(f).get("quantization_config")
+        return json.load(f).get("quantization_config") or None
+
+
+# AutoAWQ / GPTQ int4 checkpoints: every config field name, tensor suffix, the AWQ nibble order and the GPTQ zero-point convention,
+# kept in one place.  They are written from the formats' public descriptions; the config field names were compared with AwqConfig
+# and GPTQConfig of transformers (utils/quantization_config.py: bits, group_size, zero_point, version with format as its newer
+# name; bits, group_size, desc_act, sym, checkpoint_format with format as its newer name).  No AutoAWQ / auto-gptq / gptqmodel
+# package was available, so the tensor layouts have not been checked against a published checkpoint ("W4A16 with zero
+# points").
+AWQ_METHOD, GPTQ_METHOD = "awq", "gptq"
+INT4_BITS_FIELD, INT4_GROUP_FIELD = "bits", "group_size"
+AWQ_ZERO_POINT_FIELD, AWQ_VERSION_FIELDS, AWQ_VERSIONS = "zero_point", ("version", "format"), ("gemm",)
+GPTQ_DESC_ACT_FIELD, GPTQ_SYM_FIELD, GPTQ_FORMAT_FIELDS = "desc_act", "sym", ("checkpoint_format", "format")
+GPTQ_ZERO_OFFSET = {"gptq": 1, "gptq_v2": 0}       # format -> what the stored zero nibble is short of z ("gptq" stores z - 1)
+GPTQ_DEFAULT_FORMAT = "gptq"
+INT4_QWEIGHT_SUFFIX, INT4_QZEROS_SUFFIX, INT4_SCALES_SUFFIX, GPTQ_G_IDX_SUFFIX = ".qweight", ".qzeros", ".scales", ".g_idx"
+# AWQ (gemm): nibble position i (bits 4i .. 4i+3) of word j holds output column 8j + AWQ_ORDER[i], in qweight and in qzeros
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+
+
+def int4_checkpoint_scheme(qc: dict | None) -> dict | None:
+    """{"method": "awq" | "gptq", "zero_offset": 0 | 1} for the AutoAWQ / GPTQ schemes a W4A16 target runs (4 bits, groups of 128
+    columns; AWQ: zero points, gemm packing; GPTQ: no activation order, format gptq or gptq_v2, symmetric or not), None for any other
+    quant_method; every other AWQ / GPTQ variant is refused here by name."""
+    method = (qc or {}).get("quant_method")
+    if method not in (AWQ_METHOD, GPTQ_METHOD):
+        return None
+    if qc.get(INT4_BITS_FIELD) != 4:
+        raise ValueError(f"unsupported {method} {INT4_BITS_FIELD} {qc.get(INT4_BITS_FIELD)!r}: only 4-bit weights can be loaded")
+    if qc.get(INT4_GROUP_FIELD) != 128:
+        raise ValueError(f"unsupported {method} {INT4_GROUP_FIELD} {qc.get(INT4_GROUP_FIELD)!r}: only groups of 128 columns")
+    if method == AWQ_METHOD:
+        if qc.get(AWQ_ZERO_POINT_FIELD) is not True:
+            raise ValueError(f"unsupported awq {AWQ_ZERO_POINT_FIELD} {qc.get(AWQ_ZERO_POINT_FIELD)!r}: only zero_point true")
+        version = next((qc[f] for f in AWQ_VERSION_FIELDS if qc.get(f) is not None), None)
+        if str(version).lower() not in AWQ_VERSIONS:
+            raise ValueError(f"unsupported awq version {version!r}: only the gemm packing (not gemv / gemv_fast / marlin)")
+        return {"method": AWQ_METHOD, "zero_offset": 0}
+    if qc.get(GPTQ_DESC_ACT_FIELD) is not False:
+        raise ValueError(f"unsupported gptq {GPTQ_DESC_ACT_FIELD} {qc.get(GPTQ_DESC_ACT_FIELD)!r}: activation-order checkpoints "
+                         "(desc_act true, a g_idx permutation) are not supported")
+    if qc.get(GPTQ_SYM_FIELD) not in (True, False):
+        raise ValueError(f"gptq {GPTQ_SYM_FIELD} must be true or false, got {qc.get(GPTQ_SYM_FIELD)!r}")
+    fmt = next((qc[f] for f in GPTQ_FORMAT_FIELDS if qc.get(f) is not None), GPTQ_DEFAULT_FORMAT)
+    if str(fmt).lower() not in GPTQ_ZERO_OFFSET:
+        raise ValueError(f"unsupported gptq checkpoint format {fmt!r}: only {sorted(GPTQ_ZERO_OFFSET)} (not marlin / bitblas)")
+    return {"method": GPTQ_METHOD, "zero_offset": GPTQ_ZERO_OFFSET[str(fmt).lower()]}
+
+
+def checkpoint_quantization(model_dir: str) -> str | None:
+    """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales, "w4a16" for a
+    pack-quantized one with symmetric int4 weights in groups of 128 columns and for an AutoAWQ / GPTQ one (int4_checkpoint_scheme),
+    "mxfp4" for an MXFP4 one (config.json quantization_config), None for an unquantized one; every other quantization format is
+    refused here, before any tensor is read."""
+    return _checkpoint_kind(_quantization_config(model_dir))
+
+
+def _checkpoint_kind(qc: dict | None) -> str | None:
+    """checkpoint_quantization on an already parsed quantization_config."""
     if not qc:
         return None
     method = qc.get("quant_method")
+    if int4_checkpoint_scheme(qc) is not None:
+        return "w4a16"
     if method != "compressed-tensors":
         raise ValueError(f"unsupported quantization_config.quant_method {method!r}: only compressed-tensors float8 checkpoints "
-                         "(per-channel or per-tensor weight scales) and pack-quantized int4 ones (group 128) can be loaded")
+                         "(per-channel or per-tensor weight scales), pack-quantized int4 ones (group 128), MXFP4 ones, and AutoAWQ / "
+                         "GPTQ int4 ones (group 128) can be loaded")
     groups = qc.get("config_groups") or {}
     if not groups:
         raise ValueError("compressed-tensors checkpoint without config_groups")
@@ -441,6 +499,101 @@ def _w4a16_scheme(gname: str, wq: dict, fmt) -> str:
     return "w4a16"
 
 
+def _packed_sources(name: str) -> list[str] | None:
+    if "qkv_proj" in name:
+        return [name.replace("qkv_proj", s) for s in ("q_proj", "k_proj", "v_proj")]
+    if "gate_up_proj" in name:
+        return [name.replace("gate_up_proj", s) for s in ("gate_proj", "up_proj")]
+    return None
+
+
+def _unpack_nibbles(words: torch.Tensor, order=None) -> torch.Tensor:
+    """int32 [R, C] -> uint8 [R, 8 C]: nibble position i of word j is column 8j + order[i] (order None: 8j + i)."""
+    shifts = torch.arange(0, 32, 4, dtype=torch.int64, device=words.device)
+    nib = (words.to(torch.int64)[..., None] >> shifts) & 0xF                 # [R, C, 8] by nibble position
+    if order is not None:
+        out = torch.empty_like(nib)
+        out[..., torch.tensor(order, device=words.device)] = nib
+        nib = out
+    return nib.reshape(words.shape[0], -1).to(torch.uint8)
+
+
+def _load_awq_gptq(cfg: ModelConfig, model_dir: str, scheme: dict, rank: int, tp: int, out_device: str | None,
+                   w4a16: bool) -> Iterator[tuple[str, torch.Tensor]]:
+    """The AutoAWQ / GPTQ side of load_safetensors.  A quantized linear is unpacked, transposed to [N, K] and repacked on out_device,
+    one tensor at a time; q / k / v and gate / up are concatenated into the packed names.  A w4a16 target gets
+    quant.W4ZTensor(packed, scale, zero) (fp16 scales rounded to bf16 once), or the plain symmetric W4Tensor when every zero point
+    of the linear is 8; any other target gets bf16(s * (u - z)), sharded as usual.  A linear stored only as an unquantized .weight
+    (AWQ modules_to_not_convert, the LM head), norms and embeddings load as bf16."""
+    from safetensors import safe_open
+    from ssd_amd.quant import W4ZTensor, W4_GROUP, dequantize_w4zp, pack_w4u, w4z_as_symmetric
+    awq = scheme["method"] == AWQ_METHOD
+    index: dict[str, str] = {}
+    for f in sorted(glob.glob(os.path.join(model_dir, "*.safetensors"))):
+        with safe_open(f, "pt", "cpu") as sf:
+            for k in sf.keys():
+                index[k] = f
+
+    def raw(name: str) -> torch.Tensor:
+        with safe_open(index[name], "pt", "cpu") as sf:
+            t = sf.get_tensor(name)
+        return t.to(out_device) if out_device is not None else t
+
+    def get_q(base: str) -> W4ZTensor:
+        qw, qz, sc = raw(base + INT4_QWEIGHT_SUFFIX), raw(base + INT4_QZEROS_SUFFIX), raw(base + INT4_SCALES_SUFFIX)
+        if qw.dtype != torch.int32 or qz.dtype != torch.int32:
+            raise ValueError(f"{base}: qweight / qzeros are {qw.dtype} / {qz.dtype}, expected int32")
+        if sc.dtype not in (BF16, torch.float16, torch.float32):
+            raise ValueError(f"{base}{INT4_SCALES_SUFFIX} is {sc.dtype}: expected fp16, bf16 or fp32")
+        if awq:
+            K, N = qw.shape[0], qw.shape[1] * 8
+            packed = pack_w4u(_unpack_nibbles(qw, AWQ_ORDER).t().contiguous())            # [K, N] -> [N, K] -> words
+            stored = _unpack_nibbles(qz, AWQ_ORDER)
+        else:
+            K, N = qw.shape[0] * 8, qw.shape[1]
+            packed = qw.t().contiguous()             # word [j, n] = input columns 8j .. 8j+7 of output n: the row form's word [n, j]
+            stored = _unpack_nibbles(qz)
+            if base + GPTQ_G_IDX_SUFFIX in index:
+                g_idx = raw(base + GPTQ_G_IDX_SUFFIX).reshape(-1).to(torch.int64)
+                if g_idx.numel() != K or not torch.equal(g_idx, torch.arange(K, device=g_idx.device) // W4_GROUP):
+                    raise ValueError(f"{base}{GPTQ_G_IDX_SUFFIX} is not k // {W4_GROUP}: activation-order (g_idx) checkpoints are not "
+                                     "supported")
+        if K % W4_GROUP or tuple(qz.shape) != (K // W4_GROUP, N // 8) or tuple(sc.shape) != (K // W4_GROUP, N):
+            raise ValueError(f"{base}: qweight {tuple(qw.shape)}, qzeros {tuple(qz.shape)}, scales {tuple(sc.shape)} do not describe "
+                             f"a [{N}, {K}] matrix in groups of {W4_GROUP}")
+        zero = ((stored.to(torch.int16) + scheme["zero_offset"]) & 15).to(torch.uint8).t().contiguous()
+        return W4ZTensor(packed, sc.to(BF16).t().contiguous(), zero)
+
+    def get(name: str):
+        base = name[:-len(".weight")] if name.endswith(".weight") else None
+        if name not in index and base is not None and base + INT4_QWEIGHT_SUFFIX in index:
+            return get_q(base)
+        t = raw(name)
+        if not t.dtype.is_floating_point or t.element_size() == 1:
+            raise ValueError(f"{name} is {t.dtype}: expected an unquantized fp16 / bf16 / fp32 tensor")
+        return t.to(BF16)
+
+    for name, shape in param_shapes(cfg):
+        srcs = _packed_sources(name)
+        whole = name in index or name[:-len(".weight")] + INT4_QWEIGHT_SUFFIX in index
+        parts = [get(s) for s in srcs] if srcs is not None and not whole else [get(name)]
+        if all(isinstance(p, W4ZTensor) for p in parts):
+            w = W4ZTensor(*(torch.cat([p[i] for p in parts], dim=0) for i in range(3)))
+            assert (w.packed.shape[0], w.packed.shape[1] * 8) == tuple(shape), f"{name}: {tuple(w.packed.shape)} vs {shape}"
+            if w4a16:
+                yield name, w4z_as_symmetric(w)
+                continue
+            w = dequantize_w4zp(*w)
+        else:
+            if w4a16 and any(isinstance(p, W4ZTensor) for p in parts):
+                import warnings
+                warnings.warn(f"{name}: only some of {srcs} are quantized in the checkpoint; the packed matrix is dequantized and the "
+                              "w4a16 target quantizes it again on load (lossy for the parts that were int4)")
+            w = torch.cat([dequantize_w4zp(*p) if isinstance(p, W4ZTensor) else p for p in parts], dim=0)
+        assert tuple(w.shape) == tuple(shape), f"{name}: {tuple(w.shape)} != {shape}"
+        yield name, shard_param(cfg, name, w, rank, tp)
+
+
 def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 1,
                      out_device: str | None = None, fp8: bool = False, w4a16: bool = False,
                      mxfp4: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
@@ -453,11 +606,22 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
     usual, otherwise.  A W4A16 checkpoint into an fp8 target and an fp8 one into a W4A16 target are refused.
     From an MXFP4 checkpoint, a quantized linear comes as (name, MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32])) when
     ``mxfp4`` (codes and scale bytes bit for bit; scale bytes outside 2..252 are refused) and as the exact bf16 matrix
-    2^(b - 127) * e2m1(q), sharded as usual, otherwise.  MXFP4 checkpoints into fp8 / w4a16 targets and the reverse are refused."""
+    2^(b - 127) * e2m1(q), sharded as usual, otherwise.  MXFP4 checkpoints into fp8 / w4a16 targets and the reverse are refused.
+    From an AutoAWQ or GPTQ int4 checkpoint (_load_awq_gptq), a quantized linear comes as quant.W4ZTensor(packed, scale, zero) when
+    ``w4a16`` (a plain W4Tensor when all its zero points are 8) and as bf16(s * (u - z)) otherwise; fp8 and mxfp4 targets refuse it."""
     from safetensors import safe_open
     from ssd_amd.quant import FP8, dequantize_fp8, W4Tensor, dequantize_w4a16, MX4Tensor, dequantize_mxfp4, check_mxfp4_scales
     assert fp8 + w4a16 + mxfp4 <= 1
-    kind = checkpoint_quantization(model_dir)
+    qc = _quantization_config(model_dir)
+    kind = _checkpoint_kind(qc)
+    scheme = int4_checkpoint_scheme(qc)
+    if scheme is not None:
+        if fp8 or mxfp4:
+            raise ValueError(f"an {scheme['method']} int4 checkpoint cannot load into {'an fp8' if fp8 else 'an mxfp4'} target: use "
+                             "quantization='w4a16' or None")
+        assert not (w4a16 and tp > 1), "w4a16 targets are single-rank"
+        yield from _load_awq_gptq(cfg, model_dir, scheme, rank, tp, out_device, w4a16)
+        return
     ckpt_fp8 = kind == "fp8"
     if kind == "mxfp4" and (fp8 or w4a16):
         raise ValueError(f"an mxfp4 checkpoint cannot load into {'an fp8' if fp8 else 'a w4a16'} target: use quantization='mxfp4' or None")
@@ -544,15 +708,8 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
             raise ValueError(f"{name} is {t.dtype}: integer-quantized weights are not supported")
         return t.to(BF16)
 
-    def packed_sources(name: str) -> list[str] | None:
-        if "qkv_proj" in name:
-            return [name.replace("qkv_proj", s) for s in ("q_proj", "k_proj", "v_proj")]
-        if "gate_up_proj" in name:
-            return [name.replace("gate_up_proj", s) for s in ("gate_proj", "up_proj")]
-        return None
-
     for name, shape in param_shapes(cfg):
-        srcs = packed_sources(name)
+        srcs = _packed_sources(name)
         whole = name in index or name[:-len(".weight")] + ".weight_packed" in index
         parts = [get(s) for s in srcs] if srcs is not None and not whole else [get(name)]
         if all(isinstance(p, MX4Tensor) for p in parts):
