@@ -89,12 +89,13 @@ int ssd_rmsnorm_pair(const void* x0_rows, const void* weight0, const void* x1_ro
 
 /* F.linear(x, W, b) -- ssd/layers/linear.py:65,98,196; ssd/layers/embed_head.py:88,95,111.
  * x_frag [M][K] frag, w_frag [N][K] frag, bias bf16[N] or NULL.  M <= 128 per call.
- * SSD_EPI_SILU_FRAG additionally fuses SiluAndMul.forward -- ssd/layers/activation.py:11-14. */
+ * SSD_EPI_SILU_FRAG additionally fuses SiluAndMul.forward -- ssd/layers/activation.py:11-14; it needs N % 64 == 0 (the output
+ * fragment is N / 2 wide) and ignores ldy.  The row epilogues need ldy >= N. */
 int ssd_gemm_wf(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K, int ldy,
                 int epilogue, void* stream);
 /* The same F.linear for matrices with too few 16-row groups to fill the chip (csrc/gemm_sk.hip; the 1B draft's o_proj /
  * down_proj): K is split across `splits` workgroups per row group, the last one to arrive reduces the fp32 partials in a
- * fixed order.  workspace >= (N/16)*splits KiB; counters >= N/16 uint32, zeroed once.  M <= 16, bf16 rows. */
+ * fixed order.  workspace >= (N/16)*splits KiB; counters >= N/16 uint32, zeroed once.  M <= 16, bf16 rows, ldy >= N. */
 int ssd_gemm_splitk(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K, int ldy,
                     int splits, int waves, void* workspace, void* counters, void* stream);
 
@@ -102,7 +103,7 @@ int ssd_gemm_splitk(const void* x_frag, const void* w_frag, const void* bias, vo
  * split over `splits` workgroups per 16-row group, every wave keeps all its k-tiles in flight, and the partial sums are
  * NOT combined here: `parts` receives fp32 slabs [splits][M][N] which the consumer (ssd_gemm_fused_parts /
  * ssd_rmsnorm_parts) sums in slab order while forming x = bf16(sum) + residual -- the kernel boundary is the only
- * synchronisation.  parts == NULL: splits must be 1 and bf16 rows (+ bias) go to y.  ceil(K/32/splits/waves) <= 8. */
+ * synchronisation.  parts == NULL: splits must be 1 and bf16 rows (+ bias) go to y (ldy >= N).  ceil(K/32/splits/waves) <= 8. */
 int ssd_gemm_parts(const void* x_frag, const void* w_frag, const void* bias, void* y, void* parts, int M, int N, int K,
                    int ldy, int splits, int waves, void* stream);
 
@@ -110,7 +111,7 @@ int ssd_gemm_parts(const void* x_frag, const void* w_frag, const void* bias, voi
  * (ssd/engine/model_runner.py:602 -> ssd/layers/linear.py:65,98,196).  Same operands and epilogues (SSD_EPI_ROWS,
  * SSD_EPI_SILU_FRAG) as ssd_gemm_wf; the x tile of a k-step is shared by a workgroup through LDS and K is split
  * across workgroups into fp32 partials in `workspace` (>= ssd_gemm_pf_workspace_bytes), summed in a fixed order.
- * N % 128 == 0, K % 128 == 0; splits <= 0 picks the default.  epilogue 2 (partials only, y may be NULL, no bias): the fp32
+ * N % 128 == 0, K % 128 == 0; splits <= 0 picks the default; ldy >= N for SSD_EPI_ROWS.  epilogue 2 (partials only, y may be NULL, no bias): the fp32
  * partials [splits][M][N] in `workspace` ARE the output (splits = ssd_gemm_pf_workspace_bytes(M, N, K) / (4 M N)), to be
  * summed by ssd_rmsnorm_parts -- the add + RMSNorm that follows o_proj / down_proj -- instead of an epilogue launch.
  * M > 128 (a whole prompt in one launch; since ABI 3): a compute-bound tiled MFMA GEMM (256 x 256 output tiles by default, smaller

@@ -14,12 +14,15 @@ extern "C" {
 #endif
 
 /* ssd_gemm_wf with an explicit decomposition: nt = 16-row groups per workgroup (1,2,4), waves = K-split (1..16), bits 8..15 of waves =
- * consecutive tiles per workgroup; bit 8 of nt = the DEEP form (twice the k-tiles per stage; M <= 16, <= 8 waves, nt 2 / 4, epilogue 0 / 1). */
+ * consecutive tiles per workgroup; bit 8 of nt = the DEEP form (twice the k-tiles per stage; M <= 16, 1..8 waves, nt 2 / 4, epilogue 0 / 1).
+ * Refused with an error, nothing launched: any other nt; nt = 4 above 32 rows; a combine area of waves x nt x MT KiB (MT = 1 / 2 / 4 / 8
+ * for up to 16 / 32 / 64 / 128 rows) beyond the 160 KiB of LDS; ldy < N for the row epilogues; SSD_EPI_SILU_FRAG with odd nt or N % 64 != 0. */
 int ssd_gemm_wf_cfg(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K, int ldy,
                     int epilogue, int nt, int waves, void* stream);
 
 
 /* ssd_gemm_pf with an explicit decomposition: nt = 16-row groups per wave (2 or 4; a workgroup owns 4*nt), splits of K.
+ * M <= 128: ldy >= N for SSD_EPI_ROWS, and N % 64 == 0 for SSD_EPI_SILU_FRAG (3-, 5- and 7-wave workgroups admit other N).
  * M > 128: nt bits 0..7 select the long-prefill tile form -- 0 default, 1 = 256 x rows x 256 W rows (8 waves), 2 = 128 x 256
  * (8 waves), 3 = 256 x 128 (8 waves), 4 = 128 x 128 (4 waves); the other bits are ignored; splits <= 0 = the default split of the
  * default form, 1 for any other form; splits must divide K / 64. */

@@ -257,6 +257,7 @@ static int launch_t(const void* x, const void* w, const void* bias, void* y, int
   size_t lds = (size_t)waves * NT * MT * 64 * sizeof(f32x4_t);
   if (EPI == EPI_ROWS_ARGMAX) lds += (size_t)waves * MT * 16 * sizeof(ArgPart);      // per-wave argmax candidates behind the combine area
   if (DEEP && waves > 8) return SSD_ERR_ARG;
+  if (lds > 160 * 1024) return SSD_ERR_ARG;          // the LDS of a gfx950 workgroup (16 waves x NT 2 x MT 8 would be 256 KiB)
   auto kern = gemm_wf_kernel<MT, NT, EPI, DEEP>;
   if (lds > 64 * 1024) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -291,8 +292,12 @@ extern "C" int ssd_gemm_wf_cfg(const void* x_frag, const void* w_frag, const voi
   waves &= 0xff;
   const bool deep = (nt >> 8) & 1;          // bit 8 of nt: the DEEP form (M <= 16, <= 8 waves, nt 2 / 4, rows or SiLU epilogue)
   nt &= 0xff;
+  if (nt != 1 && nt != 2 && nt != 4) return SSD_ERR_ARG;          // before anything divides by it
+  if ((epilogue == EPI_ROWS || epilogue == EPI_ROWS_F32) && ldy < N) return SSD_ERR_SHAPE;
+  if (epilogue == EPI_SILU_FRAG && (N & 63)) return SSD_ERR_SHAPE;     // the output fragment is N / 2 wide: whole 32-column tiles
   if (deep) {
-    if (M > 16 || waves > 8 || (nt != 2 && nt != 4) || ((N / 16) % nt) != 0) return SSD_ERR_ARG;
+    if (M > 16 || waves < 1 || waves > 8 || nt == 1 || ((N / 16) % nt) != 0) return SSD_ERR_ARG;
+    if (!x_frag || !w_frag || !y) return SSD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (epilogue == EPI_ROWS) {
       if (nt == 2) return launch_t<1, 2, EPI_ROWS, true>(x_frag, w_frag, bias, y, M, N, K, ldy, waves, tpw, st);
@@ -307,6 +312,7 @@ extern "C" int ssd_gemm_wf_cfg(const void* x_frag, const void* w_frag, const voi
   if (waves < 1 || waves > 16) return SSD_ERR_ARG;
   if (((N / 16) % nt) != 0) return SSD_ERR_ARG;
   if (epilogue == EPI_SILU_FRAG && (nt & 1)) return SSD_ERR_ARG;
+  if (!x_frag || !w_frag || !y) return SSD_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int mt = (M + 15) / 16;
 #define DISPATCH_MT(MTV)                                                                                         \

@@ -612,6 +612,8 @@ extern "C" int ssd_gemm_pf_cfg(const void* x_frag, const void* w_frag, const voi
   if (M <= 16 || M > 128 || N <= 0 || K <= 0 || (K % (32 * PF_U))) return SSD_ERR_SHAPE;
   if (epilogue != PF_EPI_ROWS && epilogue != PF_EPI_SILU_FRAG && epilogue != PF_EPI_PARTIALS) return SSD_ERR_ARG;
   if (epilogue == PF_EPI_PARTIALS && bias) return SSD_ERR_ARG;
+  if (epilogue == PF_EPI_ROWS && ldy < N) return SSD_ERR_SHAPE;
+  if (epilogue == PF_EPI_SILU_FRAG && (N & 63)) return SSD_ERR_SHAPE;   // the output fragment is N / 2 wide: whole 32-column tiles (3-, 5-, 7-wave N)
   // nt may carry the launch shape above its low byte: waves per workgroup in bits 8..15 (0 = 4; 7 or 8 only with nt = 2),
   // W k-steps in flight per wave in bits 16..23 (0 = default), k-steps per barrier in bits 24..27 (0 = 1)
   int waves = (nt >> 8) & 0xff;
@@ -631,6 +633,7 @@ extern "C" int ssd_gemm_pf_cfg(const void* x_frag, const void* w_frag, const voi
   if (KT % (splits * PF_U) != 0) return SSD_ERR_ARG;
   const int direct = (splits == 1 && epilogue != PF_EPI_PARTIALS) ? (epilogue == PF_EPI_ROWS ? 1 : 2) : 0;     // unsplit K: finish inside the GEMM kernel
   if (!direct && (!workspace || workspace_bytes < (int64_t)splits * M * N * 4)) return SSD_ERR_ARG;
+  if (!x_frag || !w_frag || (!y && epilogue != PF_EPI_PARTIALS)) return SSD_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
   const int mt = (M + 15) / 16;

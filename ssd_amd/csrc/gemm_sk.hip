@@ -94,10 +94,11 @@ gemm_sk_kernel(const u32x4_t* __restrict__ Wf, const u32x4_t* __restrict__ Xf, c
 // them at zero).  splits in 1..8; waves in 1..16.
 extern "C" int ssd_gemm_splitk(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K, int ldy,
                                int splits, int waves, void* workspace, void* counters, void* stream) {
-  if (M <= 0 || M > 16 || (N & 15) || (K & 31) || N <= 0 || K <= 0) return SSD_ERR_SHAPE;
+  if (M <= 0 || M > 16 || (N & 15) || (K & 31) || N <= 0 || K <= 0 || ldy < N) return SSD_ERR_SHAPE;
   if (splits < 1 || splits > 8 || waves < 1 || waves > 16) return SSD_ERR_ARG;
   if (splits > 1 && (!workspace || !counters)) return SSD_ERR_ARG;
   if ((K >> 5) / splits < 1) return SSD_ERR_ARG;
+  if (!x_frag || !w_frag || !y) return SSD_ERR_ARG;
   hipLaunchKernelGGL(gemm_sk_kernel, dim3(N / 16, splits), dim3(64 * waves), (size_t)waves * 64 * sizeof(f32x4_t),
                      (hipStream_t)stream, (const u32x4_t*)w_frag, (const u32x4_t*)x_frag, (const bf16_t*)bias, (bf16_t*)y, M, N,
                      K, ldy, (unsigned long long*)workspace, (unsigned int*)counters);
@@ -190,12 +191,14 @@ extern "C" int ssd_gemm_parts(const void* x_frag, const void* w_frag, const void
   if (splits < 1 || splits > 16 || waves < 1 || waves > 16) return SSD_ERR_ARG;
   if ((parts == nullptr) == (y == nullptr)) return SSD_ERR_ARG;
   if (!parts && splits != 1) return SSD_ERR_ARG;
+  if (y && ldy < N) return SSD_ERR_SHAPE;
   const int KT = K >> 5;
   const int mt = (M + 15) / 16;
   if (KT < splits || waves < mt) return SSD_ERR_ARG;
   const int per_wg = (KT + splits - 1) / splits;
   const int tpw = (per_wg + waves - 1) / waves;
   if (tpw > 8) return SSD_ERR_ARG;
+  if (!x_frag || !w_frag) return SSD_ERR_ARG;
   const dim3 grid(N / 16, splits), block(64 * waves);
   const size_t lds = (size_t)waves * mt * 64 * sizeof(f32x4_t);
   hipStream_t st = (hipStream_t)stream;

@@ -48,6 +48,7 @@ def assert_within_ulp(got: torch.Tensor, want64: torch.Tensor, what: str, ulps: 
     bad = d > tol
     print(f"{what}: worst {(d / tol).max().item():.2f} x tol")
     assert not bool(bad.any()), f"{what}: {int(bad.sum())} outputs beyond {ulps} ulp, worst {(d / tol).max().item():.2f} x tol"
+    return (d / tol).max().item()
 
 
 def _codes(N, K, dev, seed):
@@ -167,6 +168,7 @@ def assert_silu_within_bar(y: torch.Tensor, yg: torch.Tensor, I: int, what: str)
     bad = d > tol
     print(f"{what}: worst {(d / tol).max().item():.2f} x tol")
     assert not bool(bad.any()), f"{what}: {int(bad.sum())} outputs beyond the bar, worst {(d / tol).max().item():.2f} x tol"
+    return (d / tol).max().item()
 
 
 def _check_silu(dev, M, I, K, what, seed=0):
