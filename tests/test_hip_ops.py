@@ -481,21 +481,56 @@ def make_paged(B, ctx_lens, nkv, hd, bs, seed):
     return kc, vc, bt, max_blocks
 
 
-def run_attn(H, q, kc, vc, bt, max_blocks, ctx, nh, nkv, hd, bs, cu_q=None, q_per_seq=0, splits=1, flags=0, waves=1, **tree):
+def make_paged_poisoned(B, ctx_lens, nkv, hd, bs, seed, spare=2):
+    """make_paged whose every (page, row) that is not key < ctx_lens[b] of some sequence b can be told apart: returns the clean K / V
+    (random everywhere, as make_paged), copies in which those rows -- the tail of each last page, `spare` pages no sequence owns and one
+    dedicated poison page -- are bf16 NaN in K and in V, the block table and max_blocks.  Block-table entries past a sequence's last
+    page name the poison page: allocated, in range, all NaN (no -1, no id outside the cache), so every address the kernel could form
+    stays inside the allocation.  What a recycled page may hold in service; 0 * NaN in the P.V product is NaN."""
+    g = torch.Generator().manual_seed(seed)
+    need = [(L + bs - 1) // bs for L in ctx_lens]
+    max_blocks = max(need) + 1
+    nblocks = sum(need) + spare + 1
+    perm = torch.randperm(nblocks, generator=g)
+    poison_page = int(perm[-1])
+    bt = torch.full((B, max_blocks), poison_page, dtype=torch.int32)
+    valid = torch.zeros(nblocks, bs, dtype=torch.bool)
+    p = 0
+    for b, (L, n) in enumerate(zip(ctx_lens, need)):
+        bt[b, :n] = perm[p:p + n].to(torch.int32)
+        valid.view(-1)[(perm[p:p + n].view(-1, 1) * bs + torch.arange(bs)).view(-1)[:L]] = True
+        p += n
+    kc = torch.randn(nblocks, bs, nkv, hd, generator=g).to(BF)
+    vc = torch.randn(nblocks, bs, nkv, hd, generator=g).to(BF)
+    kp, vp = kc.clone(), vc.clone()
+    kp[~valid] = float("nan")
+    vp[~valid] = float("nan")
+    return kc, vc, kp, vp, bt, max_blocks
+
+
+def run_attn_dev(H, q, kd, vd, bt, max_blocks, ctx, nh, nkv, hd, bs, cu_q=None, q_per_seq=0, splits=1, flags=0, waves=1, **tree):
+    """ssd_attn_paged on device caches in the kernels' own (HND) layout.  The split workspaces and the fragment output start as NaN
+    (the engine reuses ws_o / ws_ml across launches of different shapes: a (row, split) partial the kernel failed to write would be
+    read as whatever an earlier launch left, not as the m = 0, l = 0, O = 0 of a zero fill, which merges with weight 0 and hides)."""
     T = q.shape[0]
     B = ctx.numel()
     max_q = q_per_seq if cu_q is None else int((cu_q[1:] - cu_q[:-1]).max())
     out = torch.full((T, nh * hd), float("nan"), dtype=BF, device="cuda")
-    outf = torch.zeros(H.frag_numel(T, nh * hd), dtype=BF, device="cuda")
-    ws_o = torch.zeros(T * nh * splits * hd, dtype=torch.float32, device="cuda")
-    ws_ml = torch.zeros(T * nh * splits * 2, dtype=torch.float32, device="cuda")
-    H.attn_paged(dev(q), dev(LY.kv_nhd_to_hnd(kc)), dev(LY.kv_nhd_to_hnd(vc)), dev(bt), max_blocks, dev(ctx), B, T, max_q,
+    outf = torch.full((H.frag_numel(T, nh * hd),), float("nan"), dtype=BF, device="cuda")      # (only its first T rows are compared)
+    ws_o = torch.full((T * nh * splits * hd,), float("nan"), dtype=torch.float32, device="cuda")
+    ws_ml = torch.full((T * nh * splits * 2,), float("nan"), dtype=torch.float32, device="cuda")
+    H.attn_paged(dev(q), kd, vd, dev(bt), max_blocks, dev(ctx), B, T, max_q,
                  nh, nkv, hd, bs, hd ** -0.5, cu_q=None if cu_q is None else dev(cu_q), q_per_seq=q_per_seq, splits=splits,
                  flags=flags, ws_o=ws_o, ws_ml=ws_ml, out_rows=out, out_frag=outf, waves=waves, **tree)
     torch.cuda.synchronize()
     rows = out.cpu()
     assert torch.equal(LY.frag_to_rows_ref(outf.cpu(), T, nh * hd).view(torch.int16), rows.view(torch.int16))
     return rows
+
+
+def run_attn(H, q, kc, vc, bt, max_blocks, ctx, nh, nkv, hd, bs, **kw):
+    """run_attn_dev on caches given in the reference layout."""
+    return run_attn_dev(H, q, dev(LY.kv_nhd_to_hnd(kc)), dev(LY.kv_nhd_to_hnd(vc)), bt, max_blocks, ctx, nh, nkv, hd, bs, **kw)
 
 
 # P is rounded to bf16 before P.V (as FlashAttention-3 does in the reference): |delta o| <= 2^-9 * sum_i p_i |v_i|,
