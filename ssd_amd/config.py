@@ -84,6 +84,10 @@ class Config:
     # (quant.quantize_w4a16_zp: unsigned codes, one 4-bit zero point per row and group, run on the zero-point GEMM) instead of the
     # symmetric one.  Checkpoints that carry zero points (AutoAWQ, asymmetric GPTQ) run on that GEMM whatever this says.
     w4_zero_point: bool = False
+    # dtype of the TARGET's paged KV cache (not in the reference): None = bf16, "fp8" = OCP e4m3fn codes, one byte per element, with one
+    # fp32 scale per layer, K or V, and kv head (include/ssd_hip_kv8.h; all 1.0 unless HipDecoder.set_kv_scales is called).  Orthogonal
+    # to `quantization`.  The draft's cache, q and every activation stay bf16.
+    kv_cache_dtype: str | None = None
 
     @property
     def max_blocks(self) -> int:
@@ -104,6 +108,13 @@ class Config:
                              "not supported")
         if self.quantization is not None and self.use_eagle:
             raise ValueError(f"quantization={self.quantization!r} is not supported with use_eagle=True (EAGLE-3 taps need the bf16 "
+                             "target path)")
+        if self.kv_cache_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_cache_dtype must be None or 'fp8', got {self.kv_cache_dtype!r}")
+        if self.kv_cache_dtype is not None and self.num_gpus > 1:
+            raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r} runs on one GPU only: tensor-parallel fp8 KV caches are not supported")
+        if self.kv_cache_dtype is not None and self.use_eagle:
+            raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r} is not supported with use_eagle=True (EAGLE-3 taps need the bf16 "
                              "target path)")
         assert self.num_draft_gpus >= 1 and (self.num_draft_gpus == 1 or (self.speculate and self.draft_async)), \
             "num_draft_gpus > 1 needs draft_async"

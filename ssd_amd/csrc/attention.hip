@@ -17,6 +17,7 @@
 //                                 B = P^T, which is exactly the S^T accumulator layout -> no shuffles)
 // Split-KV partials (m, l, O) are merged by attn_combine_kernel in a fixed order.
 #include "common.h"
+#include <type_traits>
 
 struct AttnParams {
   const bf16_t* q;
@@ -40,6 +41,9 @@ struct AttnParams {
   const u32x4_t* ow;         // o_proj weights, fragment-major [oN][nh*HD]
   float* oparts;             // fp32 slabs [nkv][Tq][oN]: slab h = W_o[:, columns of kv head h's q heads] . attention output of those heads
   int oN;
+  // FP8 KV cache (attn_kernel<.., KV8 = true>, ssd_attn_paged_fp8 below): kc / vc are e4m3 codes, one fp32 scale per kv head
+  const float* k_scale;      // [nkv] or null -> 1.0
+  const float* v_scale;
 };
 
 // LDS per wave: the V tile (32 keys x HD bf16) during the scan, then the wave's partial (O fp32 [RT*16][HD],
@@ -54,8 +58,15 @@ constexpr int attn_region_bytes() { return RT * 16 * HD * 4 + RT * 16 * 8; }
 // normalised bf16 output of its heads in LDS as an MFMA B operand and multiplies: slab h of the split-K partial sums of
 // o_proj, summed by the consumer like ssd_gemm_parts' slabs.  The weight stream hides behind the attention latency chain and
 // one kernel boundary per layer disappears (a 1B draft decode layer: 6.6 us attention + 3.9 us o_proj as two launches).
-template <int HD, int RT, int KT, bool OPROJ = false>
+// KV8 (include/ssd_hip_kv8.h): the caches hold e4m3 codes, one byte per element, in the same [page][kv head][row][d] layout.  A lane
+// loads 8 bytes per (K row, k-step) and widens them to the same MFMA A operand (exact: every e4m3 value is a bf16 value); V is loaded
+// in 16-byte chunks of 16 codes and widened while it is staged into LDS as the same bf16 tile, so the transpose read, the softmax,
+// P.V, the merge and the combine are the bf16 kernel's.  k_scale[h] folds into the logit scale, v_scale[h] into the output / the
+// split partials (h is fixed per workgroup).  Rows past ctx are clamped exactly as for bf16: never addressed.
+template <int HD, int RT, int KT, bool OPROJ = false, bool KV8 = false>
 __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
+  static_assert(!(OPROJ && KV8), "no fused o_proj form over an fp8 cache");
+  constexpr int ES = KV8 ? 1 : 2;           // bytes per cache element
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KTS = OPROJ ? 7 : 6;        // trace slot (profiling builds only)
   KTRACE(KTS, 0);
@@ -80,6 +91,11 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
   const int ctx = p.context_lens[b];
   const int32_t* bt = p.block_tables + (size_t)b * p.max_blocks;
   const int z = blockIdx.z;
+  float scale_log2e = p.scale_log2e, vs = 1.0f;
+  if constexpr (KV8) {
+    if (p.k_scale) scale_log2e *= p.k_scale[h];
+    if (p.v_scale) vs = p.v_scale[h];
+  }
 
   // ---- per-lane query-row descriptors and Q fragments ----
   u32x4_t qf[RT][DS];
@@ -125,7 +141,7 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
     for (int dt = 0; dt < DT; ++dt) o[rt][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
 
-  constexpr int CH = HD / 8;             // 16-byte chunks per key row
+  constexpr int CH = HD * ES / 16;       // 16-byte chunks per key row
   constexpr int NV = (32 * CH) / 64;     // V chunks per lane per tile
   // page-table entries of a tile are wave-uniform (scalar loads): keys k..k+15 share a page and so do k+16..k+31
   // (block sizes are multiples of 16); a key clamped to ctx-1 falls into one of the two.  The index is clamped to
@@ -139,19 +155,24 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
   // clamped to the last valid row of the tile (never an unwritten row, never an unallocated page): if the second half
   // starts at or past ctx it is redirected to the first half's page.
   auto half_base = [&](const bf16_t* base, int page, int key0) -> const char* {
-    return reinterpret_cast<const char*>(base + (((size_t)page * p.nkv + h) * p.bs + (key0 & (p.bs - 1))) * HD);
+    return reinterpret_cast<const char*>(base) + (((size_t)page * p.nkv + h) * p.bs + (key0 & (p.bs - 1))) * (HD * ES);
   };
-  auto issue_k = [&](int kt, int pa, int pb, u32x4_t (&kf)[2][DS]) {
+  // K operand of one (16-key half, k-step) as loaded: 8 bf16, or 8 codes that kwide() widens in front of the MFMA
+  using kraw_t = typename std::conditional<KV8, u32x2_t, u32x4_t>::type;
+  auto kwide = [](const kraw_t& k) -> u32x4_t {
+    if constexpr (KV8) return kv8_to_bf16x8(k[0], k[1]); else return k;
+  };
+  auto issue_k = [&](int kt, int pa, int pb, kraw_t (&kf)[2][DS]) {
     const int cl = ctx - 1 - kt;                  // >= 0 for every tile we touch
     const bool bvalid = cl >= 16;
     const char* b0 = half_base(p.kc, pa, kt);
     const char* b1 = bvalid ? half_base(p.kc, pb, kt + 16) : b0;
-    const uint32_t o0 = (uint32_t)(min(r16, cl) * HD + g4 * 8) * 2u;
-    const uint32_t o1 = (uint32_t)(min(r16, bvalid ? cl - 16 : cl) * HD + g4 * 8) * 2u;
+    const uint32_t o0 = (uint32_t)(min(r16, cl) * HD + g4 * 8) * (uint32_t)ES;
+    const uint32_t o1 = (uint32_t)(min(r16, bvalid ? cl - 16 : cl) * HD + g4 * 8) * (uint32_t)ES;
 #pragma unroll
     for (int ds = 0; ds < DS; ++ds) {
-      kf[0][ds] = *reinterpret_cast<const u32x4_t*>(b0 + o0 + ds * 64);
-      kf[1][ds] = *reinterpret_cast<const u32x4_t*>(b1 + o1 + ds * 64);
+      kf[0][ds] = *reinterpret_cast<const kraw_t*>(b0 + o0 + ds * 32 * ES);
+      kf[1][ds] = *reinterpret_cast<const kraw_t*>(b1 + o1 + ds * 32 * ES);
     }
   };
   auto issue_v = [&](int kt, int pa, int pb, u32x4_t (&vf)[NV]) {
@@ -166,7 +187,7 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
       const int key = it * KPI + lane / CH;       // 0..31; the half is static per `it`
       const bool second = (it * KPI) >= 16;
       const int r = second ? min(key - 16, clb) : min(key, cl);
-      const uint32_t off = (uint32_t)(r * HD + (lane % CH) * 8) * 2u;
+      const uint32_t off = (uint32_t)(r * HD * ES + (lane % CH) * 16);
       vf[it] = *reinterpret_cast<const u32x4_t*>((second ? b1 : b0) + off);
     }
   };
@@ -175,7 +196,8 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
   // the tile KT ahead as soon as they have been consumed (the loads fly during the softmax and P.V of this and the
   // following tiles); the page entries for that refill were fetched (scalar loads) one round earlier.
   constexpr bool PIPE_K = !(HD == 128 && RT == 2);   // the widest variant has no registers to hold K ahead of time
-  u32x4_t kreg[KT][2][DS], vreg[KT][NV];
+  kraw_t kreg[KT][2][DS];
+  u32x4_t vreg[KT][NV];
   int ca[KT], cb[KT], na[KT], nb[KT];
 #pragma unroll
   for (int j = 0; j < KT; ++j) {
@@ -212,8 +234,15 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
 #pragma unroll
     for (int it = 0; it < NV; ++it) {
       const int c = it * 64 + lane;
-      const int key = c / CH, d8 = c % CH;
-      *reinterpret_cast<u32x4_t*>(vlds + ((d8 >> 1) * 32 + key) * 16 + (d8 & 1) * 8) = vreg[j][it];
+      if constexpr (KV8) {     // a chunk is 16 codes = one whole [key] row of the [32 keys][16 d] sub-tile c % CH
+        const int key = c / CH, d16 = c % CH;
+        bf16_t* dst = vlds + (d16 * 32 + key) * 16;
+        *reinterpret_cast<u32x4_t*>(dst) = kv8_to_bf16x8(vreg[j][it][0], vreg[j][it][1]);
+        *reinterpret_cast<u32x4_t*>(dst + 8) = kv8_to_bf16x8(vreg[j][it][2], vreg[j][it][3]);
+      } else {
+        const int key = c / CH, d8 = c % CH;
+        *reinterpret_cast<u32x4_t*>(vlds + ((d8 >> 1) * 32 + key) * 16 + (d8 & 1) * 8) = vreg[j][it];
+      }
     }
     if (more) issue_v(kn, na[j], nb[j], vreg[j]);
     // -- S^T = K . Q^T --
@@ -224,7 +253,7 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
       for (int rt = 0; rt < RT; ++rt) {
         st[hf][rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ds = 0; ds < DS; ++ds) st[hf][rt] = mfma16(kreg[j][hf][ds], qf[rt][ds], st[hf][rt]);
+        for (int ds = 0; ds < DS; ++ds) st[hf][rt] = mfma16(kwide(kreg[j][hf][ds]), qf[rt][ds], st[hf][rt]);
       }
     }
     if constexpr (PIPE_K) { if (more) issue_k(kn, na[j], nb[j], kreg[j]); }
@@ -253,7 +282,7 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
             vis = vis || (rel > p.tree_K && ((rel - p.tree_K - 1) % p.tree_mq) == tl[rt]);  // own branch diagonal
             ok = ok && vis;
           }
-          const float v = ok ? st[hf][rt][r] * p.scale_log2e : -INFINITY;
+          const float v = ok ? st[hf][rt][r] * scale_log2e : -INFINITY;
           s[hf * 4 + r] = v;
           tmax = fmaxf(tmax, v);
         }
@@ -329,7 +358,8 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
       const float l = lsum[rt];
       const size_t row = (size_t)(q0 + tl[rt]) * p.nh + hq[rt];
       if (p.splits == 1) {
-        const float inv = l > 0.f ? 1.0f / l : 0.f;
+        float inv = l > 0.f ? 1.0f / l : 0.f;
+        if constexpr (KV8) inv *= vs;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
           const int d = dt * 16 + g4 * 4;
@@ -343,7 +373,7 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
       } else {
         float* wo = p.ws_o + (row * p.splits + z) * HD;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4_t*>(wo + dt * 16 + g4 * 4) = o[rt][dt];
+        for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4_t*>(wo + dt * 16 + g4 * 4) = KV8 ? o[rt][dt] * vs : o[rt][dt];
         if (g4 == 0) {
           p.ws_ml[(row * p.splits + z) * 2] = m[rt];
           p.ws_ml[(row * p.splits + z) * 2 + 1] = l;
@@ -406,7 +436,8 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
       const int kl = (rho % G) * HD + d;
       reinterpret_cast<u32x2_t*>(smem + (size_t)W * REGION)[(((kl >> 3) << 4) + rho / G) * 2 + ((kl >> 2) & 1)] = v;
     } else if (p.splits == 1) {
-      const float inv = L > 0.f ? 1.0f / L : 0.f;
+      float inv = L > 0.f ? 1.0f / L : 0.f;
+      if constexpr (KV8) inv *= vs;
       const u32x2_t v = {pack_bf2(acc[0] * inv, acc[1] * inv), pack_bf2(acc[2] * inv, acc[3] * inv)};
       if (p.out_rows) *reinterpret_cast<u32x2_t*>(p.out_rows + row * HD + d) = v;
       if (p.out_frag) {
@@ -414,7 +445,7 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
         p.out_frag[frag_chunk(tok, kcol >> 3, (p.nh * HD) >> 5) * 2 + ((kcol >> 2) & 1)] = v;
       }
     } else {
-      *reinterpret_cast<f32x4_t*>(p.ws_o + (row * p.splits + z) * HD + d) = acc;
+      *reinterpret_cast<f32x4_t*>(p.ws_o + (row * p.splits + z) * HD + d) = KV8 ? acc * vs : acc;
       if (d == 0) {
         p.ws_ml[(row * p.splits + z) * 2] = M;
         p.ws_ml[(row * p.splits + z) * 2 + 1] = L;
@@ -470,10 +501,10 @@ __global__ void attn_combine_kernel(const float* __restrict__ ws_o, const float*
   }
 }
 
-template <int HD, int RT, int KT>
+template <int HD, int RT, int KT, bool KV8>
 static int attn_launch_rt(const AttnParams& p, dim3 grid, int waves, hipStream_t st) {
   const int lds = waves * attn_region_bytes<HD, RT>();
-  auto kern = attn_kernel<HD, RT, KT, false>;
+  auto kern = attn_kernel<HD, RT, KT, false, KV8>;
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
     return SSD_ERR_LAUNCH;
@@ -483,7 +514,7 @@ static int attn_launch_rt(const AttnParams& p, dim3 grid, int waves, hipStream_t
 
 // Row tiles per workgroup: two for prefill-sized query blocks (> 8 tiles; K/V bytes shared by 32 rows), one for the decode-side
 // shapes (more workgroups: the scan is bound by per-CU load bandwidth and latency, not by K/V bytes).
-template <int HD>
+template <int HD, bool KV8>
 static int attn_launch(const AttnParams& p, int B, int T, int max_q, int waves, int force_rt1, hipStream_t st) {
   const int G = p.nh / p.nkv;
   const int row_tiles = (max_q * G + 15) / 16;
@@ -493,7 +524,7 @@ static int attn_launch(const AttnParams& p, int B, int T, int max_q, int waves, 
   dim3 grid(B * p.nkv, (row_tiles + rt - 1) / rt, p.splits);
   // one key tile in flight per wave (KT = 1): measured on MI355X, KT = 2/4 buy nothing -- with 8 waves per workgroup
   // the scan is bound by the handful of CUs it occupies, not by a single wave's load latency
-  const int rc = rt == 2 ? attn_launch_rt<HD, 2, 1>(p, grid, waves, st) : attn_launch_rt<HD, 1, 1>(p, grid, waves, st);
+  const int rc = rt == 2 ? attn_launch_rt<HD, 2, 1, KV8>(p, grid, waves, st) : attn_launch_rt<HD, 1, 1, KV8>(p, grid, waves, st);
   if (rc != SSD_OK) return rc;
   if (p.splits > 1) {
     hipLaunchKernelGGL((attn_combine_kernel<HD>), dim3(T * p.nh), dim3(HD / 4), 0, st, p.ws_o, p.ws_ml, p.splits, p.nh,
@@ -528,6 +559,7 @@ extern "C" int ssd_attn_oproj_parts(const void* q_rows, const void* k_cache, con
   p.splits = 1; p.use_tr = 1; p.p_split = 1;
   p.scale_log2e = scale * 1.4426950408889634f;
   p.ow = (const u32x4_t*)w_o_frag; p.oparts = (float*)parts; p.oN = N;
+  p.k_scale = nullptr; p.v_scale = nullptr;
   const dim3 grid(nkv * (N / 128), 1, 1), block(512);
   hipStream_t st = (hipStream_t)stream;
   const int rt = rows > 16 ? 2 : 1;
@@ -546,12 +578,13 @@ extern "C" int ssd_attn_oproj_parts(const void* q_rows, const void* k_cache, con
   return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
 }
 
-extern "C" int ssd_attn_paged(const void* q_rows, const void* k_cache, const void* v_cache,
-                              const int32_t* block_tables, int max_blocks, const int32_t* context_lens,
-                              const int32_t* cu_q, int q_per_seq, int B, int T, int max_q, int nh, int nkv, int hd,
-                              int block_size, float scale, int mode, int tree_K, int tree_mq, int tree_step,
-                              int tree_F, const int32_t* tree_jidx, int splits, int flags, void* ws_o, void* ws_ml,
-                              void* out_rows, void* out_frag, void* stream) {
+template <bool KV8>
+static int attn_paged_impl(const void* q_rows, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale,
+                           const int32_t* block_tables, int max_blocks, const int32_t* context_lens,
+                           const int32_t* cu_q, int q_per_seq, int B, int T, int max_q, int nh, int nkv, int hd,
+                           int block_size, float scale, int mode, int tree_K, int tree_mq, int tree_step,
+                           int tree_F, const int32_t* tree_jidx, int splits, int flags, void* ws_o, void* ws_ml,
+                           void* out_rows, void* out_frag, void* stream) {
   if (B <= 0 || T <= 0 || max_q <= 0 || nh <= 0 || nkv <= 0 || nh % nkv) return SSD_ERR_SHAPE;
   if (hd != 64 && hd != 128) return SSD_ERR_SHAPE;
   if (block_size < 16 || (block_size & (block_size - 1)) != 0 || max_blocks <= 0) return SSD_ERR_SHAPE;
@@ -569,6 +602,7 @@ extern "C" int ssd_attn_paged(const void* q_rows, const void* k_cache, const voi
   p.splits = splits; p.use_tr = (flags & 1) ? 0 : 1; p.p_split = (flags & 2) ? 0 : 1;
   p.scale_log2e = scale * 1.4426950408889634f;
   p.ow = nullptr; p.oparts = nullptr; p.oN = 0;
+  p.k_scale = k_scale; p.v_scale = v_scale;
   hipStream_t st = (hipStream_t)stream;
   // flags bits 8..11: waves per workgroup that split the key range and merge in LDS (default 1; 1..8)
   int waves = (flags >> 8) & 0xf;
@@ -576,7 +610,39 @@ extern "C" int ssd_attn_paged(const void* q_rows, const void* k_cache, const voi
   if (waves > 8) waves = 8;
   // flags bit 2: one 16-row tile per workgroup even for wider query blocks (twice the workgroups for the 24-branch tree)
   const int rt1 = (flags >> 2) & 1;
-  return hd == 128 ? attn_launch<128>(p, B, T, max_q, waves, rt1, st) : attn_launch<64>(p, B, T, max_q, waves, rt1, st);
+  return hd == 128 ? attn_launch<128, KV8>(p, B, T, max_q, waves, rt1, st) : attn_launch<64, KV8>(p, B, T, max_q, waves, rt1, st);
+}
+
+extern "C" int ssd_attn_paged(const void* q_rows, const void* k_cache, const void* v_cache,
+                              const int32_t* block_tables, int max_blocks, const int32_t* context_lens,
+                              const int32_t* cu_q, int q_per_seq, int B, int T, int max_q, int nh, int nkv, int hd,
+                              int block_size, float scale, int mode, int tree_K, int tree_mq, int tree_step,
+                              int tree_F, const int32_t* tree_jidx, int splits, int flags, void* ws_o, void* ws_ml,
+                              void* out_rows, void* out_frag, void* stream) {
+  return attn_paged_impl<false>(q_rows, k_cache, v_cache, nullptr, nullptr, block_tables, max_blocks, context_lens, cu_q, q_per_seq, B, T,
+                                max_q, nh, nkv, hd, block_size, scale, mode, tree_K, tree_mq, tree_step, tree_F, tree_jidx, splits, flags,
+                                ws_o, ws_ml, out_rows, out_frag, stream);
+}
+
+// ---- FP8 KV cache (include/ssd_hip_kv8.h): the target's causal shapes only -- decode, verify, varlen prefill ----
+extern "C" int ssd_attn_paged_fp8(const void* q_rows, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale,
+                                  const int32_t* block_tables, int max_blocks, const int32_t* context_lens, const int32_t* cu_q,
+                                  int q_per_seq, int B, int T, int max_q, int nh, int nkv, int hd, int block_size, float scale, int mode,
+                                  int tree_K, int tree_mq, int tree_step, int tree_F, const int32_t* tree_jidx, int splits, int flags,
+                                  void* ws_o, void* ws_ml, void* out_rows, void* out_frag, void* stream) {
+  if (!q_rows || !k_cache || !v_cache || !block_tables || !context_lens || (!out_rows && !out_frag)) return SSD_ERR_ARG;
+  if (mode != 0) return SSD_ERR_ARG;        // the tree mask is the draft's, and the draft's cache is bf16
+  return attn_paged_impl<true>(q_rows, k_cache, v_cache, k_scale, v_scale, block_tables, max_blocks, context_lens, cu_q, q_per_seq, B, T,
+                               max_q, nh, nkv, hd, block_size, scale, 0, 0, 0, 0, 1, nullptr, splits, flags, ws_o, ws_ml, out_rows,
+                               out_frag, stream);
+}
+extern "C" int ssd_attn_prefill_varlen_fp8(const void* q_rows, const void* k_cache, const void* v_cache, const float* k_scale,
+                                           const float* v_scale, const int32_t* block_tables, int max_blocks,
+                                           const int32_t* context_lens, const int32_t* cu_q, int B, int T, int max_q, int nh, int nkv,
+                                           int hd, int block_size, float scale, void* out_rows, void* out_frag, void* stream) {
+  if (!cu_q) return SSD_ERR_ARG;
+  return ssd_attn_paged_fp8(q_rows, k_cache, v_cache, k_scale, v_scale, block_tables, max_blocks, context_lens, cu_q, 0, B, T, max_q, nh,
+                            nkv, hd, block_size, scale, 0, 0, 0, 0, 1, nullptr, 1, 0, nullptr, nullptr, out_rows, out_frag, stream);
 }
 
 // The reference's two other attention call sites under their own names (SURVEY section 8b's list): thin forms of ssd_attn_paged, which already

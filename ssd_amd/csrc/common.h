@@ -21,8 +21,31 @@ constexpr int SSD_MAX_DEVICES = 16;  // per-device host-side caches (function at
 #include "ssd_hip_w4a16.h"
 #include "ssd_hip_w4zp.h"
 #include "ssd_hip_mxfp4.h"
+#include "ssd_hip_kv8.h"
 
 __device__ __forceinline__ float bf2f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
+
+// FP8 KV cache (include/ssd_hip_kv8.h): code = e4m3fn_rne(clamp(x * inv_scale, -448, 448)).  The clamp comes first: the converter's
+// behaviour past 448 is a mode bit, and the format has no infinity.  A NaN stays a NaN (fminf / fmaxf alone would turn it into 448).
+__device__ __forceinline__ float kv8_clamp(float v) {
+  const float c = fminf(fmaxf(v, -448.f), 448.f);
+  return v != v ? v : c;
+}
+// four values -> four codes, value i in byte i
+__device__ __forceinline__ uint32_t kv8_encode4(float a, float b, float c, float d, float inv) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(a * inv), kv8_clamp(b * inv), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(c * inv), kv8_clamp(d * inv), w, true);
+  return (uint32_t)w;
+}
+// 8 codes (two 32-bit words) -> the 8 bf16 of one MFMA operand slice; every e4m3 value is a bf16 value, so this is exact
+__device__ __forceinline__ u32x4_t kv8_to_bf16x8(uint32_t w0, uint32_t w1) {
+  u32x4_t r;
+  r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
+  r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
+  r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
+  r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
+  return r;
+}
 
 // fp32 -> bf16, round-to-nearest-even (the rounding every torch bf16 store performs).
 __device__ __forceinline__ uint32_t f2bf(float f) {

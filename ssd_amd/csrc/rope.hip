@@ -12,13 +12,16 @@
 // PARTS: the QKV rows are not materialised -- the prefill GEMM (gemm_pf.hip, PF_EPI_PARTIALS) left S fp32 split-K slabs
 // parts[s][t][n]; a row's value is bf16(slab 0 + slab 1 + ... in that order), exactly what gemm_pf_epilogue_kernel would have
 // stored, so the result is bit-identical to "epilogue launch, then this kernel" with one launch less per layer.
-template <bool PARTS>
+// KV8: the caches are e4m3 codes, one byte per element (include/ssd_hip_kv8.h); only the two cache stores differ -- the value that
+// would have been stored as bf16 is multiplied by the kv head's inverse scale, clamped to +-448 and rounded to e4m3.
+template <bool PARTS, bool KV8 = false>
 __global__ void rope_store_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ parts, int S, size_t slab,
                                   const int64_t* __restrict__ positions,
                                   const float* __restrict__ cos_sin, const int32_t* __restrict__ slots,
                                   bf16_t* __restrict__ q_out, bf16_t* __restrict__ k_cache,
                                   bf16_t* __restrict__ v_cache, const bf16_t* __restrict__ qn_w,
-                                  const bf16_t* __restrict__ kn_w, float eps, int nh, int nkv, int hd, int bs, int perm) {
+                                  const bf16_t* __restrict__ kn_w, float eps, int nh, int nkv, int hd, int bs, int perm,
+                                  const float* __restrict__ k_inv = nullptr, const float* __restrict__ v_inv = nullptr) {
   const int t = blockIdx.x;
   const int c16 = hd >> 4;                 // threads per rotated head (each owns 8+8 elements)
   const int rot_items = (nh + nkv) * c16;  // q and k heads
@@ -99,9 +102,21 @@ __global__ void rope_store_kernel(const bf16_t* __restrict__ qkv, const float* _
         *reinterpret_cast<u32x4_t*>(dst + c * 8) = o1;
         *reinterpret_cast<u32x4_t*>(dst + half + c * 8) = o2;
       } else if (kv_base >= 0) {
-        bf16_t* dst = k_cache + (size_t)(kv_base + (long)(head - nh) * bs) * hd;
-        *reinterpret_cast<u32x4_t*>(dst + c * 8) = o1;
-        *reinterpret_cast<u32x4_t*>(dst + half + c * 8) = o2;
+        if constexpr (KV8) {
+          const float inv = k_inv ? k_inv[head - nh] : 1.0f;
+          uint8_t* dst = reinterpret_cast<uint8_t*>(k_cache) + (size_t)(kv_base + (long)(head - nh) * bs) * hd;
+          // (the bf16 rounding of the bf16 cache first: o1 / o2 hold exactly those values)
+          *reinterpret_cast<u32x2_t*>(dst + c * 8) =
+              u32x2_t{kv8_encode4(bf2f(o1[0] & 0xffffu), bf2f(o1[0] >> 16), bf2f(o1[1] & 0xffffu), bf2f(o1[1] >> 16), inv),
+                      kv8_encode4(bf2f(o1[2] & 0xffffu), bf2f(o1[2] >> 16), bf2f(o1[3] & 0xffffu), bf2f(o1[3] >> 16), inv)};
+          *reinterpret_cast<u32x2_t*>(dst + half + c * 8) =
+              u32x2_t{kv8_encode4(bf2f(o2[0] & 0xffffu), bf2f(o2[0] >> 16), bf2f(o2[1] & 0xffffu), bf2f(o2[1] >> 16), inv),
+                      kv8_encode4(bf2f(o2[2] & 0xffffu), bf2f(o2[2] >> 16), bf2f(o2[3] & 0xffffu), bf2f(o2[3] >> 16), inv)};
+        } else {
+          bf16_t* dst = k_cache + (size_t)(kv_base + (long)(head - nh) * bs) * hd;
+          *reinterpret_cast<u32x4_t*>(dst + c * 8) = o1;
+          *reinterpret_cast<u32x4_t*>(dst + half + c * 8) = o2;
+        }
       }
     } else if (kv_base >= 0) {
       const int vi = it - rot_items;
@@ -114,7 +129,14 @@ __global__ void rope_store_kernel(const bf16_t* __restrict__ qkv, const float* _
       } else {
         v = *reinterpret_cast<const u32x4_t*>(row + (size_t)(nh + nkv + kvh) * hd + c * 8);
       }
-      *reinterpret_cast<u32x4_t*>(v_cache + (size_t)(kv_base + (long)kvh * bs) * hd + c * 8) = v;
+      if constexpr (KV8) {
+        const float inv = v_inv ? v_inv[kvh] : 1.0f;
+        *reinterpret_cast<u32x2_t*>(reinterpret_cast<uint8_t*>(v_cache) + (size_t)(kv_base + (long)kvh * bs) * hd + c * 8) =
+            u32x2_t{kv8_encode4(bf2f(v[0] & 0xffffu), bf2f(v[0] >> 16), bf2f(v[1] & 0xffffu), bf2f(v[1] >> 16), inv),
+                    kv8_encode4(bf2f(v[2] & 0xffffu), bf2f(v[2] >> 16), bf2f(v[3] & 0xffffu), bf2f(v[3] >> 16), inv)};
+      } else {
+        *reinterpret_cast<u32x4_t*>(v_cache + (size_t)(kv_base + (long)kvh * bs) * hd + c * 8) = v;
+      }
     }
   }
 }
@@ -161,4 +183,44 @@ extern "C" int ssd_rope_store_kv_parts(const float* parts, int splits, const int
   if (!parts || splits < 1 || splits > 16) return SSD_ERR_ARG;
   return rope_store_launch(nullptr, parts, splits, positions, cos_sin, slot_mapping, q_out_rows, k_cache, v_cache, q_norm_w,
                            k_norm_w, eps, T, nh, nkv, hd, block_size, qkv_perm, stream);
+}
+
+// ---- FP8 KV cache (include/ssd_hip_kv8.h) ----
+extern "C" int ssd_rope_store_kv_fp8(const void* qkv_rows, const int64_t* positions, const float* cos_sin, const int32_t* slot_mapping,
+                                     void* q_out_rows, void* k_cache, void* v_cache, const float* k_inv_scale, const float* v_inv_scale,
+                                     const void* q_norm_w, const void* k_norm_w, float eps, int T, int nh, int nkv, int hd, int block_size,
+                                     int qkv_perm, void* stream) {
+  if (!qkv_rows || !positions || !cos_sin || !q_out_rows || !k_cache || !v_cache) return SSD_ERR_ARG;
+  if (T <= 0 || nh <= 0 || nkv <= 0 || (hd != 64 && hd != 128) || block_size <= 0) return SSD_ERR_SHAPE;
+  const int items = (nh + nkv) * (hd / 16) + nkv * (hd / 8);
+  int threads = ((items + 63) / 64) * 64;
+  if (threads > 512) threads = 512;
+  hipLaunchKernelGGL((rope_store_kernel<false, true>), dim3(T), dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv_rows,
+                     (const float*)nullptr, 0, (size_t)0, positions, cos_sin, slot_mapping, (bf16_t*)q_out_rows, (bf16_t*)k_cache,
+                     (bf16_t*)v_cache, (const bf16_t*)q_norm_w, (const bf16_t*)k_norm_w, eps, nh, nkv, hd, block_size, qkv_perm,
+                     k_inv_scale, v_inv_scale);
+  return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
+}
+
+// bf16(scale[h] * code) over whole pages: one thread per 8 codes
+__global__ void kv8_dequant_kernel(const uint32_t* __restrict__ c8, const float* __restrict__ scale, u32x4_t* __restrict__ out,
+                                   size_t n8, int nkv, int per_head8) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n8) return;
+  const float s = scale ? scale[(i / per_head8) % nkv] : 1.0f;
+  const u32x4_t w = kv8_to_bf16x8(c8[2 * i], c8[2 * i + 1]);
+  u32x4_t r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = pack_bf2(bf2f(w[j] & 0xffffu) * s, bf2f(w[j] >> 16) * s);
+  out[i] = r;
+}
+
+extern "C" int ssd_kv_fp8_dequant(const void* cache8, const float* scale, void* cache_bf16, int pages, int nkv, int block_size, int hd,
+                                  void* stream) {
+  if (!cache8 || !cache_bf16) return SSD_ERR_ARG;
+  if (pages <= 0 || nkv <= 0 || block_size <= 0 || (hd != 64 && hd != 128)) return SSD_ERR_SHAPE;
+  const size_t n8 = (size_t)pages * nkv * block_size * hd / 8;
+  hipLaunchKernelGGL(kv8_dequant_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint32_t*)cache8, scale, (u32x4_t*)cache_bf16, n8, nkv, block_size * hd / 8);
+  return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
 }

@@ -65,6 +65,10 @@ class ModelRunner:
         qkw = {"quantization": quantization} if quantization else {}
         if quantization == "w4a16" and getattr(config, "w4_zero_point", False):
             qkw["w4_zero_point"] = True
+        # ... and so does the fp8 KV cache
+        kv_cache_dtype = None if is_draft else getattr(config, "kv_cache_dtype", None)
+        if kv_cache_dtype:
+            qkw["kv_cache_dtype"] = kv_cache_dtype
         self.model = model_cls(model_cfg, max_tokens=max_tokens, max_seqs=self.max_bs, max_blocks=self.max_blocks,
                                block_size=self.block_size, max_model_len=config.max_model_len, device=device,
                                tp_rank=tp_rank, tp_size=tp_size, tp_group=tp_group,

@@ -24,6 +24,7 @@ from ssd_amd.hip import quant_ops as Q
 from ssd_amd.hip import w4_ops as W4
 from ssd_amd.hip import w4zp_ops as W4Z
 from ssd_amd.hip import mx4_ops as MX4
+from ssd_amd.hip import kv8_ops as KV8
 from ssd_amd import quant
 from ssd_amd.model_config import ModelConfig
 
@@ -62,8 +63,20 @@ class HipDecoder:
     def __init__(self, cfg: ModelConfig, *, max_tokens: int, max_seqs: int, max_blocks: int, block_size: int,
                  max_model_len: int, device: torch.device, tp_rank: int = 0, tp_size: int = 1, tp_group=None,
                  max_logit_rows: int | None = None, max_split_tokens: int = 256, force_collectives: bool = False,
-                 taps: list[int] | None = None, quantization: str | None = None, w4_zero_point: bool = False):
+                 taps: list[int] | None = None, quantization: str | None = None, w4_zero_point: bool = False,
+                 kv_cache_dtype: str | None = None):
         self.cfg, self.device = cfg, device
+        # kv_cache_dtype="fp8": the paged KV cache holds e4m3 codes, one byte per element, with one fp32 scale per layer, K or V, and kv
+        # head (include/ssd_hip_kv8.h; all 1.0 until set_kv_scales).  Orthogonal to `quantization`.  Every form that writes or reads KV
+        # inside another kernel is off -- the QKV + RoPE epilogue of gemm_fused (and with it the fused norm prologues, whose residual
+        # ping-pong starts in that launch), attention + o_proj, the chain / tree segments, the QKV prefill partials -- so a layer is
+        # QKV rows -> ssd_rope_store_kv_fp8 -> ssd_attn_paged_fp8; o / down partial slabs and the prefill forms stay as they are.
+        if kv_cache_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_cache_dtype must be None or 'fp8', got {kv_cache_dtype!r}")
+        self.kv8 = kv_cache_dtype == "fp8"
+        if self.kv8 and cfg.head_dim not in (64, 128):
+            raise ValueError(f"kv_cache_dtype='fp8' needs head_dim 64 or 128, got {cfg.head_dim}")
+        assert not self.kv8 or (tp_size == 1 and not force_collectives and taps is None), "fp8 KV caches are single-rank, without taps"
         # quantization="fp8": the decoder linears are e4m3 codes + per-row fp32 scales (ssd_amd/quant.py) and run on csrc/gemm_fp8.hip;
         # every bf16-only fused form (norm prologues, the QKV+RoPE epilogue, split-K slabs, attention + o_proj, the resident chain /
         # tree segments, prefill partials) is off, so a layer is norm -> GEMM -> RoPE / KV store -> attention -> GEMM -> norm -> GEMM
@@ -146,6 +159,11 @@ class HipDecoder:
         self.pf_parts = True
         if self.quantized:
             self.use_parts = self.fuse_attn_o = self.pf_parts = False
+        if self.kv8:
+            self.fuse_attn_o = False
+        # fp8 KV: scale and inverse-scale tables fp32 [L][2 (K | V)][nkv], allocated once (hipGraphs bake the pointers)
+        self.kv_scale = torch.ones(cfg.num_layers, 2, self.nkv, dtype=torch.float32, device=device) if self.kv8 else None
+        self.kv_inv_scale = torch.ones_like(self.kv_scale) if self.kv8 else None
         # the single-token chain (one sequence, T = 1) with everything between two attention launches in ONE resident launch
         # (csrc/chain.hip): 1 + 2 per layer launches instead of 4 per layer
         # Default ("auto"): on at the geometry it was validated and measured at on the MI355X -- Llama-3.2-1B's, the draft of every
@@ -156,7 +174,7 @@ class HipDecoder:
         _geo = (self.h, self.qn, self.I, self.qkv_n, self.hd)
         _validated = _geo == (2048, 2048, 8192, 3072, 64)
         self.chain_seg = ((_cs == "1" or (_cs == "auto" and _validated)) and not cfg.qk_norm and tp_size == 1 and not self.use_coll and not self.quantized
-                          and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
+                          and not self.kv8 and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         # the same segment for 2..30 token rows (csrc/tree_segment.hip): attention + ONE resident launch per layer instead of 7
         # launches.  Measured on MI355X at the 1B draft's geometry (profiles/r05_tree_seg_probe_v1.txt, parity tests/test_hip_tree_segment.py):
         # the K+1 = 8-row glue decode 0.945 -> 0.857 ms (kept), the 24-row tree step 0.943 -> 0.965 ms (NOT kept: at 24 rows every
@@ -172,7 +190,7 @@ class HipDecoder:
         #  is all there is: tree step 1.248 -> 1.240 ms at 6 rows, 1.275 -> 1.299 at 12, 1.363 -> 1.457 at 24,
         #  profiles/r05_tree_seg_probe_qwen.txt -- so "auto" leaves it off there)
         self.tree_seg = ((_ts == "1" or (_ts == "auto" and _validated)) and tp_size == 1 and not self.use_coll and not self.quantized
-                         and taps is None and max_tokens >= 2
+                         and not self.kv8 and taps is None and max_tokens >= 2
                          and H.tree_segment_ok(2, self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         if self.chain_seg:
             self.chain_gr = z(H.chain_granule_bytes(self.h, self.I) // 8, dtype=torch.int64)
@@ -384,13 +402,43 @@ class HipDecoder:
         return sum(t.numel() * t.element_size() for n, t in self.w.items() if n != "model.embed_tokens.weight")
 
     def kv_block_bytes(self) -> int:
-        return 2 * self.cfg.num_layers * self.block_size * self.nkv * self.hd * 2
+        return 2 * self.cfg.num_layers * self.block_size * self.nkv * self.hd * (1 if self.kv8 else 2)
 
     def alloc_kv(self, num_blocks: int) -> None:
         # [L][2][blocks][nkv][block_size][hd]: one (page, kv head) is a contiguous run for the attention kernel
         self.num_blocks = num_blocks
         self.kv_cache = torch.zeros(self.cfg.num_layers, 2, num_blocks, self.nkv, self.block_size, self.hd,
-                                    dtype=BF16, device=self.device)
+                                    dtype=torch.uint8 if self.kv8 else BF16, device=self.device)
+
+    def set_kv_scales(self, k_scale: torch.Tensor, v_scale: torch.Tensor) -> None:
+        """fp8 KV cache: per layer and kv head scales, fp32 [L, nkv] each (positive, finite).  Copied INTO the device tables (their
+        pointers are baked into hipGraphs); the inverse the store multiplies by is computed here in fp32.  Codes already in the
+        cache keep the scale they were stored with: set the scales before the first forward."""
+        if not self.kv8:
+            raise ValueError("set_kv_scales needs kv_cache_dtype='fp8'")
+        L = self.cfg.num_layers
+        ks = torch.as_tensor(k_scale, dtype=torch.float32).reshape(L, self.nkv)
+        vs = torch.as_tensor(v_scale, dtype=torch.float32).reshape(L, self.nkv)
+        s = torch.stack([ks, vs], dim=1)
+        if not (torch.isfinite(s).all() and (s > 0).all()):
+            raise ValueError("KV scales must be positive and finite")
+        self.kv_scale.copy_(s)
+        self.kv_inv_scale.copy_(1.0 / s)
+
+    def _attn(self, li: int, T: int, meta: AttnMeta, splits: int, flags: int, waves: int, scale: float) -> None:
+        """The layer's paged attention launch into buf_af, over the bf16 or the fp8 cache."""
+        if self.kv8:
+            assert meta.mode == H.MODE_CAUSAL, "the fp8 KV cache serves the target's causal shapes only"
+            KV8.attn_paged_fp8(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
+                               meta.context_lens, meta.B, T, meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale,
+                               k_scale=self.kv_scale[li, 0], v_scale=self.kv_scale[li, 1], cu_q=meta.cu_q, q_per_seq=meta.q_per_seq,
+                               splits=splits, flags=flags, ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=waves)
+            return
+        H.attn_paged(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
+                     meta.context_lens, meta.B, T, meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale,
+                     cu_q=meta.cu_q, q_per_seq=meta.q_per_seq, mode=meta.mode, tree_K=meta.tree_K, tree_mq=meta.tree_mq,
+                     tree_step=meta.tree_step, tree_F=meta.tree_F, tree_jidx=meta.tree_jidx, splits=splits,
+                     flags=flags, ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=waves)
 
     # ---------------------------------------------------------------------------------------------
     PF_MIN_WEIGHT_BYTES = 100 << 20
@@ -584,7 +632,7 @@ class HipDecoder:
         between producer and norm: the prologue is paid by EVERY workgroup and its LDS image limits residency --
         measured on MI355X, M=7 x K=4096 made gate_up 73 us vs 49 us unfused, M=1 x K=2048 made norm+qkv+rope 5.6 us
         vs 14.8 us."""
-        small = T <= 16 and not self.cfg.qk_norm and not self.quantized
+        small = T <= 16 and not self.cfg.qk_norm and not self.quantized and not self.kv8
         return small, small and not self.use_coll and T * self.h // 8 <= 1024
 
     def chain_plan(self, T: int, meta: AttnMeta, splits: int) -> bool:
@@ -692,10 +740,10 @@ class HipDecoder:
             else:
                 H.rmsnorm(h, w[p + "input_layernorm.weight"], cfg.rms_norm_eps, T, self.h, res_in=None if li == 0 else res,
                           res_out=res, out_frag=xf)
-        if small or (16 < T <= 32 and not cfg.qk_norm and not self.quantized):      # T in 17..32 (tree-decode step): the two-token-tile variant
+        if small or (16 < T <= 32 and not cfg.qk_norm and not self.quantized and not self.kv8):      # T in 17..32 (tree-decode step): the two-token-tile variant
             H.gemm_fused(w[p + "self_attn.qkv_proj.weight"], T, self.qkv_n, self.h, H.FEPI_QKV_ROPE, x_frag=xf,
                          bias=w.get(p + "self_attn.qkv_proj.bias"), **rope)
-        elif (not gemm_only and w.get(p + "self_attn.qkv_proj.bias") is None and self._pf_partials_ok(T, self.qkv_n, self.h)
+        elif (not gemm_only and not self.kv8 and w.get(p + "self_attn.qkv_proj.bias") is None and self._pf_partials_ok(T, self.qkv_n, self.h)
               and self._pf_splits(T, self.qkv_n, self.h) > 1):
             # single-chunk prefill of a big QKV matrix: its split-K slabs stay in the workspace and the RoPE / KV-store kernel
             # sums them (bit-identical to the GEMM's epilogue launch + rope_store_kv; one launch less per layer)
@@ -708,6 +756,12 @@ class HipDecoder:
                        bias=w.get(p + "self_attn.qkv_proj.bias"), scale=w.get(p + "self_attn.qkv_proj.weight_scale"),
                        zero=w.get(p + "self_attn.qkv_proj.weight_zero"))
             if gemm_only:
+                return
+            if self.kv8:
+                KV8.rope_store_kv_fp8(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
+                                      self.hd, self.block_size, k_inv_scale=self.kv_inv_scale[li, 0], v_inv_scale=self.kv_inv_scale[li, 1],
+                                      q_norm_w=w.get(p + "self_attn.q_norm.weight"), k_norm_w=w.get(p + "self_attn.k_norm.weight"),
+                                      eps=cfg.rms_norm_eps, qkv_perm=1)
                 return
             H.rope_store_kv(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
                             self.hd, self.block_size, q_norm_w=w.get(p + "self_attn.q_norm.weight"),
@@ -810,11 +864,7 @@ class HipDecoder:
                                    meta.context_lens, T, self.nh, self.nkv, self.hd, self.block_size, scale,
                                    w[f"model.layers.{li}.self_attn.o_proj.weight"], self.h, self.buf_parts_o)
             else:
-                H.attn_paged(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
-                             meta.context_lens, meta.B, T, meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale,
-                             cu_q=meta.cu_q, q_per_seq=meta.q_per_seq, mode=meta.mode, tree_K=meta.tree_K, tree_mq=meta.tree_mq,
-                             tree_step=meta.tree_step, tree_F=meta.tree_F, tree_jidx=meta.tree_jidx, splits=splits,
-                             flags=attn_flags, ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=attn_waves)
+                self._attn(li, T, meta, splits, attn_flags, attn_waves, scale)
                 pf_o = self.launch_o(li, T, parts=parts, pf_partials=not parts)
             if fuse:
                 ar.all_reduce_add_rmsnorm(h, res, res, w[f"model.layers.{li}.post_attention_layernorm.weight"], eps, T, self.h, out_frag=xf)

@@ -258,3 +258,24 @@ def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     v = lut[unpack_mxfp4(packed).long()]
     s = (scale.to(torch.int32) << 23).view(torch.float32).repeat_interleave(MX4_BLOCK, dim=1)
     return (v * s).to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# FP8 KV cache (kv_cache_dtype="fp8", include/ssd_hip_kv8.h): e4m3fn codes, one byte per element, one fp32 scale per layer, K or V,
+# and kv head.  The definition the kernels are tested against, in torch, on any device.
+# ---------------------------------------------------------------------------------------------------------------------
+def kv_fp8_encode(x_bf16: torch.Tensor, inv_scale) -> torch.Tensor:
+    """uint8 codes of bf16 values [..., hd]: e4m3fn_rne(clamp(fp32(x) * inv_scale, -448, 448)).  inv_scale is an fp32 scalar or a
+    tensor that broadcasts against x (per kv head: shape [..., nkv, 1, 1] for the cache layout [..., nkv, block_size, hd]).  The clamp
+    comes first: torch's float8_e4m3fn cast rounds to nearest even and keeps -0.0 but does not saturate (500.0 becomes NaN)."""
+    assert x_bf16.dtype == torch.bfloat16, x_bf16.dtype
+    inv = torch.as_tensor(inv_scale, dtype=torch.float32, device=x_bf16.device)
+    y = (x_bf16.float() * inv).clamp(-FP8_MAX, FP8_MAX)
+    return y.to(FP8).view(torch.uint8)
+
+
+def kv_fp8_decode(codes: torch.Tensor, scale) -> torch.Tensor:
+    """fp32 values scale * fp32(code) of uint8 codes (the widening is exact; codes 0x7F and 0xFF are NaN)."""
+    assert codes.dtype == torch.uint8, codes.dtype
+    s = torch.as_tensor(scale, dtype=torch.float32, device=codes.device)
+    return s * codes.view(FP8).float()
