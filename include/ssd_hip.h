@@ -288,7 +288,9 @@ int ssd_verify_greedy(const int64_t* preds, const int64_t* speculations, int B, 
  * accept_prob (optional) float[B][K] receives min(1, p/q) per position.
  * sampler_x (apply_sampler_x_rescaling -- ssd/utils/async_helpers/async_spec_helpers.py:79-105; sampler.py:29-31;
  * verify.py:101-105): boost_idx int32[rows][boost_k] = the F+1 most probable tokens of each row (ssd_topk_rows),
- * boost_x = sampler_x; NULL disables it.  ssd_row_lse and ssd_verify_ratio must see the same boost rows for q. */
+ * boost_x = sampler_x; NULL disables it.  ssd_row_lse and ssd_verify_ratio must see the same boost rows for q.
+ * Every token id these write lies in [0, V): a row with nothing comparable in it (all NaN) yields 0, as ssd_argmax_rows does.
+ * The random stream is a function of (seed word, salt, row, element index) in which no two of salt, row and index alias. */
 int ssd_topk_rows(const void* logits_rows, long ld, int T, int V, int k, int32_t* out_idx, void* stream);
 int ssd_sample_rows(const void* logits_rows, long ld, int T, int V, const float* temps, int rows_per_temp,
                     const void* rng_state, unsigned salt, int64_t* out, int64_t* out2, const int32_t* boost_idx,

@@ -17,9 +17,15 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
   return z ^ (z >> 31);
 }
-// uniform in (0, 1), 24 bits
+// uniform in (0, 1), 24 bits.  The key word holds salt[0:24) | row[0:8) | idx, one field per bit range; whatever of salt and row does
+// not fit (row >= 256: the tree step samples B * mq rows; salt >= 2^24) goes through a mix64 round of its own, so (salt, row, idx)
+// -> stream is injective up to the hash and row 256 under salt s is no longer row 0 under salt s + 1.  Rows < 256 under salts
+// < 2^24 (everything the engine drew before) keep their streams bit for bit.
 __device__ __forceinline__ float u01(uint64_t seed, uint32_t salt, uint32_t row, uint32_t idx) {
-  const uint64_t h = mix64(seed ^ mix64(((uint64_t)salt << 40) ^ ((uint64_t)row << 20 << 12) ^ idx));
+  uint64_t z = mix64(((uint64_t)(salt & 0xffffffu) << 40) ^ ((uint64_t)(row & 0xffu) << 32) ^ idx);
+  const uint64_t hi = ((uint64_t)(salt >> 24) << 24) | (row >> 8);
+  if (hi) z = mix64(z ^ hi);
+  const uint64_t h = mix64(seed ^ z);
   return ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
 }
 __device__ __forceinline__ float gumbel(float u) { return -__logf(-__logf(u)); }
@@ -36,6 +42,7 @@ __device__ Best block_best(Best best, Best* sm) {
   __syncthreads();
   Best r = sm[0];
   for (int w = 1; w < THREADS / 64; ++w) r = bmax(r, sm[w]);
+  if (r.i == 0x7fffffff) r.i = 0;   // nothing comparable in the row (all NaN): never emit the sentinel as a token id (as block_row_argmax)
   return r;
 }
 template <int THREADS>
