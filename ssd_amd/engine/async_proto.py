@@ -8,6 +8,8 @@ three-plus-logits:
   payload int64[payload_len]
      speculate: keys[B,3] (seq_id, accepted_draft_tokens j, recovery token) | num_tokens[B] |
                 draft block tables[B, max_blocks] (-1 padded) | temperature bits[B]
+                + top_k[B] | top_p bits[B] | min_p bits[B] at the very end, only when flags & FLAG_FILTER (some sequence of
+                the batch has a logit filter: the draft truncates its q as the target truncates its p)
      prefill:   token ids (all sequences, concatenated) | num_tokens[B] | draft block tables[B, max_blocks]
   reply (speculate only) int64[B + B*K] = cache_hits[B] | tokens[B,K]
      + bf16 logits_q[B,K,V] only when flags & FLAG_WANT_LOGITS (some temperature > 0): at temperature 0 verify()
@@ -34,6 +36,7 @@ import torch.distributed as dist
 CMD_SPECULATE, CMD_PREFILL, CMD_EXIT, CMD_HELLO = 0, 1, 2, 3
 FLAG_WANT_LOGITS = 1
 FLAG_EAGLE = 2
+FLAG_FILTER = 4
 HEADER_LEN = 4
 
 
@@ -47,7 +50,8 @@ def bits_temp(b: int) -> float:
 
 def pack_speculate(keys: list[tuple[int, int, int]], num_tokens: list[int], block_tables: list[list[int]],
                    temps: list[float], max_blocks: int, extend_counts: list[int] | None = None,
-                   extend_ids: list[list[int]] | None = None) -> list[int]:
+                   extend_ids: list[list[int]] | None = None, *, filters=None) -> list[int]:
+    """filters: None (the payload is exactly the one without the feature) or (top_k [B], top_p [B], min_p [B])."""
     out: list[int] = []
     for k in keys:
         out.extend(k)
@@ -60,11 +64,23 @@ def pack_speculate(keys: list[tuple[int, int, int]], num_tokens: list[int], bloc
         out.extend(extend_counts)
         for row in extend_ids:
             out.extend(row)
+    if filters is not None:
+        top_k, top_p, min_p = filters
+        out.extend(int(k) for k in top_k)
+        out.extend(temp_bits(p) for p in top_p)
+        out.extend(temp_bits(m) for m in min_p)
     return out
 
 
-def unpack_speculate(payload: list[int], B: int, max_blocks: int, K: int | None = None):
-    """K given: the payload carries the EAGLE extend block; returns two more values (counts [B], ids [B][K])."""
+def unpack_speculate(payload: list[int], B: int, max_blocks: int, K: int | None = None, *, filters: bool = False):
+    """K given: the payload carries the EAGLE extend block; returns two more values (counts [B], ids [B][K]).
+    filters=True (flags & FLAG_FILTER): the payload ends in the filter block; returns one more value, the tuple
+    (top_k [B], top_p [B], min_p [B])."""
+    tail = ()
+    if filters:
+        blk = payload[len(payload) - 3 * B:]
+        payload = payload[:len(payload) - 3 * B]
+        tail = (([int(k) for k in blk[:B]], [bits_temp(x) for x in blk[B:2 * B]], [bits_temp(x) for x in blk[2 * B:]]),)
     off = 0
     keys = [tuple(payload[off + 3 * b: off + 3 * b + 3]) for b in range(B)]
     off += 3 * B
@@ -80,9 +96,9 @@ def unpack_speculate(payload: list[int], B: int, max_blocks: int, K: int | None 
         ids = [payload[off + b * K: off + (b + 1) * K] for b in range(B)]
         off += B * K
         assert off == len(payload)
-        return keys, num_tokens, tables, temps, counts, ids
+        return (keys, num_tokens, tables, temps, counts, ids) + tail
     assert off == len(payload)
-    return keys, num_tokens, tables, temps
+    return (keys, num_tokens, tables, temps) + tail
 
 
 def pack_prefill(token_lists: list[list[int]], block_tables: list[list[int]], max_blocks: int) -> list[int]:

@@ -186,8 +186,9 @@ class DraftServer:
         dp = self.dp
         lead = dp is None or dp.rank == 0
         eagle = None
+        has_f = bool(flags & P.FLAG_FILTER)
         if flags & P.FLAG_EAGLE:
-            keys, num_tokens, tables, temps, ext_counts, ext_ids = P.unpack_speculate(payload, B, self.max_blocks, K)
+            keys, num_tokens, tables, temps, ext_counts, ext_ids, *rest = P.unpack_speculate(payload, B, self.max_blocks, K, filters=has_f)
             cfg = self.runner.cfg
             acts = self.tx.recv_tensor((B, K + 1, cfg.eagle_taps * cfg.d_model_target), torch.bfloat16)
             # every draft position is one behind the sequence (pos_offset = -1, draft_runner.py:133-135,409,497): the
@@ -195,7 +196,10 @@ class DraftServer:
             num_tokens = [n - 1 for n in num_tokens]
             eagle = dict(acts=acts, ext_counts=ext_counts, ext_ids=ext_ids)
         else:
-            keys, num_tokens, tables, temps = P.unpack_speculate(payload, B, self.max_blocks)
+            keys, num_tokens, tables, temps, *rest = P.unpack_speculate(payload, B, self.max_blocks, filters=has_f)
+        # the request's logit filters reach the runner as a keyword, and only when the block is there: runners without the feature
+        # (the oracle runners of the CPU tests, EAGLE-3 drafts) are never called with it
+        fkw = {"filters": rest[0]} if (rest and eagle is None) else {}
         if self._trace is not None:
             self._trace.flush(f"round={self.stats['rounds']} hits={self.stats['hits']}/{self.stats['requests']}")
             t_req = self._trace.mark()
@@ -254,7 +258,7 @@ class DraftServer:
                 tokens = self.runner.draft_jit(rec, num_tokens, tables, temps, cond=eagle["acts"][:, K])
                 eagle["prev_acts"] = self.runner.jit_acts(B)
             elif lead:
-                tokens = self.runner.draft_jit(rec, num_tokens, tables, temps)  # [B, K] on the draft device
+                tokens = self.runner.draft_jit(rec, num_tokens, tables, temps, **fkw)  # [B, K] on the draft device
                 self._check_segments(True)      # the chain segment: its tokens leave with the reply below (misses only: one word read back)
                 if want_logits and sample:
                     logits_q = self.runner.logits_q(B)
@@ -293,7 +297,7 @@ class DraftServer:
                 self.cache_tokens = self.runner.draft_tree(forks, num_tokens, tables, jl, temps, eagle=True)
                 self.cache_acts = self.runner.tree_acts(forks.numel())
             else:
-                self.cache_tokens = self.runner.draft_tree(forks, num_tokens, tables, jl, temps)  # [B*mq', K]
+                self.cache_tokens = self.runner.draft_tree(forks, num_tokens, tables, jl, temps, **fkw)  # [B*mq', K]
             self.cache_logits = self.runner.tree_logits(forks.numel()) if sample else None
             self.pending_forks = forks
             self.pending_meta = ([k[0] for k in keys], jl)

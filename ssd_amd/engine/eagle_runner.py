@@ -165,12 +165,12 @@ class EagleDraftRunner(ModelRunner):
         return self.d_forks[:B].clone()
 
     # ---- tree: branch i starts from the glue prenorm of its position j_i, then conditions on its own previous step ----
-    def _body_tree(self, B: int, d: int, sample: bool = False, mq: int | None = None) -> None:
+    def _body_tree(self, B: int, d: int, sample: bool = False, mq: int | None = None, filt: bool = False) -> None:
         m = self.model
         T = B * (mq or self.mq)
         if d == 0:
             torch.index_select(self.d_glue_pre, 0, self.d_cond_idx[:T], out=m.buf_cond[:T])
-        super()._body_tree(B, d, sample, mq)
+        super()._body_tree(B, d, sample, mq, filt)      # (greedy-only: sample and filt are always False here)
         self.d_tree_acts[:T, d].copy_(m.buf_pre[:T])
         m.buf_cond[:T].copy_(m.buf_pre[:T])
 

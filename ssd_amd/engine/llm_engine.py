@@ -180,6 +180,12 @@ class LLMEngine:
             if self.tokenizer is None:
                 raise ValueError("string prompts need a tokenizer in the model directory; pass token-id lists")
             prompt = self.tokenizer.encode(prompt)
+        active = sampling_params.active_filters if sampling_params is not None else []
+        if active:      # top_k / top_p / min_p need a runner that truncates the sampled rows (the HIP runners do)
+            for runner in (getattr(self, "model_runner", None), self.draft_runner):
+                if runner is not None and not getattr(runner, "supports_logit_filters", False):
+                    raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no logit filter "
+                                     f"(requested: {', '.join(active)})")
         self.scheduler.add(Sequence(prompt, sampling_params))
 
     def step(self, step: InferenceStep):

@@ -18,6 +18,7 @@ import torch
 import torch.distributed as dist
 
 from ssd_amd.hip import ops as H
+from ssd_amd.hip import filter_ops as HF
 from ssd_amd.hip.lib import load_library
 from ssd_amd.model import HipDecoder, AttnMeta
 from ssd_amd.model_config import ModelConfig
@@ -29,6 +30,7 @@ from ssd_amd.engine.async_proto import to_device
 class ModelRunner:
     PREFILL_GRAPHS = 4              # prefill shapes kept as hipGraphs
     PREFILL_GRAPH_MAX_T = 1024      # longer prefills are GPU-bound by far: launch overhead does not matter
+    supports_logit_filters = True   # top_k / top_p / min_p (csrc/filter.hip); LLMEngine.add_request refuses them on runners without it
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
                  tp_size: int = 1, tp_group=None, model_path: str | None = None, weights_seed: int = 0,
@@ -186,6 +188,10 @@ class ModelRunner:
         self.d_temps = torch.zeros(B, dtype=torch.float32, **dev)       # temperatures this model samples with
         self.d_temps_q = torch.zeros(B, dtype=torch.float32, **dev)     # (target) the draft's temperatures
         self.d_ratio = torch.zeros(B, dtype=torch.int32, **dev)
+        # logit filter (csrc/filter.hip), one entry per sequence beside d_temps; uploaded only by steps that have a filtered sequence
+        self.d_top_k = torch.zeros(B, dtype=torch.int32, **dev)
+        self.d_top_p = torch.ones(B, dtype=torch.float32, **dev)
+        self.d_min_p = torch.zeros(B, dtype=torch.float32, **dev)
         self.d_lse_p = torch.zeros(B * (K + 1), dtype=torch.float32, **dev)
         self.d_lse_q = torch.zeros(B * K, dtype=torch.float32, **dev)
         if self.is_draft:
@@ -357,7 +363,7 @@ class ModelRunner:
         are keyed by its power-of-two bucket because the attention decomposition is fixed at capture."""
         self._ctx_hint = HipDecoder.ctx_bucket(max_ctx)
 
-    def _body_decode(self, B: int, chain: bool, head: bool = True, sample: bool = False) -> None:
+    def _body_decode(self, B: int, chain: bool, head: bool = True, sample: bool = False, filt: bool = False) -> None:
         self.model.forward(self.d_ids, self.d_pos, B, self._meta("decode", B))
         if not head:        # KV deposit only (the (K+1)-th draft forward, speculator_sync.py:55-56): no LM head / sampling
             return
@@ -365,6 +371,8 @@ class ModelRunner:
         if sample:          # temperature > 0: keep logits_q for the ratio test and draw with the Gumbel-max sampler
             lg = self.model.full_logits(B)
             V = self.cfg.vocab_size
+            if filt:        # before anything reads the rows: the stored logits_q, the boost rows and the draw see the truncated row
+                self._filter(lg, B, 1)
             if chain:
                 H.store_step_rows(lg, V, self.d_logits_q, B, V, self.K, self.d_step)
             if chain and self.is_draft and self.sx is not None:
@@ -387,7 +395,7 @@ class ModelRunner:
             H.draft_advance(self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                             self.block_size, self.d_spec, self.K, self.d_step, B)
 
-    def _body_verify(self, B: int, greedy_tail: bool, logits_q=None) -> None:
+    def _body_verify(self, B: int, greedy_tail: bool, logits_q=None, filt: bool = False) -> None:
         T = B * (self.K + 1)
         self.model.forward(self.d_ids, self.d_pos, T, self._meta("verify", B))
         self.model.compute_logits(T)
@@ -395,6 +403,8 @@ class ModelRunner:
             K, V = self.K, self.cfg.vocab_size
             lg = self.model.full_logits(T)
             self.model.argmax(T, self.d_next)
+            if filt:        # the target's p only: logits_q was truncated once, where the draft sampled from it
+                self._filter(lg, T, K + 1)
             H.row_lse(lg, V, T, V, self.d_temps, K + 1, self.d_lse_p)
             boost = {}
             if self.sx is not None:          # verify.py:101-105: q is the sampler_x-rescaled draft distribution
@@ -499,9 +509,13 @@ class ModelRunner:
         if any(t > 0 for t in temps):       # autoregressive sampling (AutoRegressiveStep at temperature > 0)
             self._ensure_stochastic()
             self._upload(self.d_temps, temps, torch.float32)
-            if self._launch(("decode_s", B), lambda: self._body_decode(B, False, sample=True)) == "captured":
+            filters = self._seq_filters(seqs)
+            if filters is not None:
+                self._upload_filters(filters)
+            key = ("decode_sf" if filters is not None else "decode_s", B)
+            if self._launch(key, lambda: self._body_decode(B, False, sample=True, filt=filters is not None)) == "captured":
                 self._prepare_decode(seqs)
-                self.graphs[("decode_s", B, self._ctx_hint)].replay()
+                self.graphs[(*key, self._ctx_hint)].replay()
         elif self._launch(("decode", B), lambda: self._body_decode(B, False)) == "captured":
             self._prepare_decode(seqs)
             self.graphs[("decode", B, self._ctx_hint)].replay()
@@ -532,13 +546,37 @@ class ModelRunner:
         return [float(s.draft_temperature) if (self.is_draft and s.draft_temperature is not None) else float(s.temperature)
                 for s in seqs]
 
+    @staticmethod
+    def _seq_filters(seqs):
+        """(top_k [B], top_p [B], min_p [B]) of the batch, or None when no sequence has a filter (then nothing is launched)."""
+        f = ([int(getattr(s, "top_k", 0)) for s in seqs], [float(getattr(s, "top_p", 1.0)) for s in seqs],
+             [float(getattr(s, "min_p", 0.0)) for s in seqs])
+        on = any(k > 0 for k in f[0]) or any(p < 1.0 for p in f[1]) or any(m > 0.0 for m in f[2])
+        return f if on else None
+
+    def _upload_filters(self, filters) -> None:
+        self._upload(self.d_top_k, list(filters[0]), torch.int32)
+        self._upload(self.d_top_p, list(filters[1]), torch.float32)
+        self._upload(self.d_min_p, list(filters[2]), torch.float32)
+
+    def _filter(self, lg: torch.Tensor, rows: int, rows_per_param: int) -> None:
+        """Truncate `rows` sampled rows in place, one parameter set (d_temps, d_top_k, d_top_p, d_min_p) per rows_per_param rows.
+        Rows of temperature 0 and rows whose sequence has no filter come back untouched."""
+        V = self.cfg.vocab_size
+        HF.filter_rows(lg, V, rows, V, self.d_temps, self.d_top_k, self.d_top_p, self.d_min_p, rows_per_param)
+
     def _sample_or_argmax(self, seqs, B: int) -> None:
         temps = self._seq_temps(seqs)
         if any(t > 0 for t in temps):
             self._ensure_stochastic()
             self._upload(self.d_temps, temps, torch.float32)
             V = self.cfg.vocab_size
-            H.sample_rows(self.model.full_logits(B), V, B, V, self.d_temps, 1, self.d_rng, 3, self.d_next)
+            lg = self.model.full_logits(B)
+            filters = self._seq_filters(seqs)
+            if filters is not None:
+                self._upload_filters(filters)
+                self._filter(lg, B, 1)
+            H.sample_rows(lg, V, B, V, self.d_temps, 1, self.d_rng, 3, self.d_next)
             H.rng_advance(self.d_rng)
         else:
             self.model.argmax(B, self.d_next)
@@ -560,7 +598,9 @@ class ModelRunner:
         self._check_chain_host()
         temps = self._seq_temps(seqs)
         sample = any(t > 0 for t in temps)
-        key = ("decode_chain_s" if sample else "decode_chain", B)
+        filters = self._seq_filters(seqs) if sample else None
+        filt = filters is not None
+        key = (("decode_chain_sf" if filt else "decode_chain_s") if sample else "decode_chain", B)
         if sample:
             self._ensure_stochastic()
 
@@ -570,10 +610,12 @@ class ModelRunner:
             self.d_spec[:B, 0].copy_(self.d_ids[:B])
             if sample:
                 self._upload(self.d_temps, temps, torch.float32)
+            if filt:
+                self._upload_filters(filters)
 
         def chain():                     # all K forwards in ONE hipGraph: no host gap between them
             for _ in range(K):
-                self._body_decode(B, True, sample=sample)
+                self._body_decode(B, True, sample=sample, filt=filt)
 
         stage()
         if self._launch(key, chain) == "captured":
@@ -609,7 +651,9 @@ class ModelRunner:
         B, K = len(seqs), self.K
         self._acts_sliced = None
         stochastic = temps_q is not None
-        key = ("verify_s" if stochastic else "verify", B)
+        filters = self._seq_filters(seqs) if stochastic else None
+        filt = filters is not None
+        key = (("verify_sf" if filt else "verify_s") if stochastic else "verify", B)
         if stochastic:
             self._ensure_stochastic()
             if logits_q is None:        # greedy draft under a sampling target: q is one-hot, its logits are never read
@@ -618,7 +662,7 @@ class ModelRunner:
                 logits_q = self._lq_dummy[:B]
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
             if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):
-                self.graphs = {k: v for k, v in self.graphs.items() if k[0] != "verify_s"}   # pointer is baked in the graph
+                self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in ("verify_s", "verify_sf")}   # pointer is baked in the graph
             self._lq_ptr = logits_q.data_ptr()
 
         def stage():
@@ -628,9 +672,11 @@ class ModelRunner:
                 self._upload(self.d_temps, self._seq_temps(seqs), torch.float32)
                 self._upload(self.d_temps_q, [float(t) for t in temps_q], torch.float32)
                 self._upload(self.d_ratio, [int(r) for r in ratio_rows], torch.int32)
+            if filt:
+                self._upload_filters(filters)
 
         stage()
-        if self._launch(key, lambda: self._body_verify(B, True, logits_q=logits_q)) == "captured":
+        if self._launch(key, lambda: self._body_verify(B, True, logits_q=logits_q, filt=filt)) == "captured":
             stage()
             self.graphs[(*key, self._ctx_hint)].replay()
         self._log_margins(B * (K + 1), [(s.seq_id, s.num_tokens - (K + 1) + j + 1) for s in seqs for j in range(K + 1)])
@@ -708,13 +754,15 @@ class ModelRunner:
         return B, T, max_q
 
     @torch.inference_mode()
-    def draft_jit(self, rec, num_tokens, tables, temps=None) -> torch.Tensor:
+    def draft_jit(self, rec, num_tokens, tables, temps=None, filters=None) -> torch.Tensor:
         """K chained single-token decodes from the recovery token at P = n - 1 (no host sync).  With some
-        temperature > 0 the tokens are sampled and the K rows of draft logits are kept for `logits_q`."""
+        temperature > 0 the tokens are sampled and the K rows of draft logits are kept for `logits_q`; filters
+        (top_k [B], top_p [B], min_p [B]) truncates them first, as the target truncates its p."""
         B, K = len(rec), self.K
         self._check_chain_host()
         sample = temps is not None and any(t > 0 for t in temps)
-        key = ("decode_chain_s" if sample else "decode_chain", B)
+        filt = sample and filters is not None
+        key = (("decode_chain_sf" if filt else "decode_chain_s") if sample else "decode_chain", B)
         self._note_ctx(max(num_tokens) + self._async_lookahead())
         if sample:
             self._ensure_stochastic()
@@ -729,10 +777,12 @@ class ModelRunner:
             self.d_step.zero_()
             if sample:
                 self._upload(self.d_temps, list(temps), torch.float32)
+            if filt:
+                self._upload_filters(filters)
 
         def chain():
             for _ in range(K):
-                self._body_decode(B, True, sample=sample)
+                self._body_decode(B, True, sample=sample, filt=filt)
 
         stage()
         if self._launch(key, chain) == "captured":
@@ -805,7 +855,7 @@ class ModelRunner:
         self._post_chain_err()
         return self.d_forks[:B].clone()
 
-    def _body_tree(self, B: int, d: int, sample: bool = False, mq: int | None = None) -> None:
+    def _body_tree(self, B: int, d: int, sample: bool = False, mq: int | None = None, filt: bool = False) -> None:
         mq = mq or self.mq          # tree width: MQ_LEN, or one member's slice of it under draft data-parallelism
         T = B * mq
         meta = AttnMeta(H.MODE_TREE, B, mq, self.d_tree_slots[d], self.d_tree_ctx[d], self.d_bt, q_per_seq=mq,
@@ -816,6 +866,8 @@ class ModelRunner:
         if sample:          # one temperature per sequence = per MQ_LEN branch rows; keep every branch's logits for logits_q
             V = self.cfg.vocab_size
             lg = self.model.full_logits(T)
+            if filt:        # one parameter set per sequence = per mq branch rows
+                self._filter(lg, T, mq)
             H.store_step_rows(lg, V, self.d_tree_logits, T, V, self.K, self.d_steps_const[d:])
             if self.sx is not None:          # Sampler(is_tree=True) with sampler_x (sampler.py:29-31)
                 H.topk_rows(lg, V, T, V, self.sx_k, self.d_boost)
@@ -834,15 +886,17 @@ class ModelRunner:
         self.d_tree_tokens[:T, d].copy_(self.d_next[:T])
 
     @torch.inference_mode()
-    def draft_tree(self, forks: torch.Tensor, num_tokens, tables, jlists, temps=None) -> torch.Tensor:
+    def draft_tree(self, forks: torch.Tensor, num_tokens, tables, jlists, temps=None, filters=None) -> torch.Tensor:
         """K tree-decode steps with the structural branch mask; tokens (greedy, or sampled when some temperature is
-        > 0) are chained on the device.  Returns tokens [B*MQ, K]; the branches' logits stay in `tree_logits`."""
+        > 0, from rows truncated by `filters` when given) are chained on the device.  Returns tokens [B*MQ, K]; the
+        branches' logits stay in `tree_logits`."""
         self._ensure_tree_buffers()
         B, K, mq = forks.shape[0], self.K, forks.shape[1]      # mq < MQ_LEN: one member's branch slice (draft data-parallelism)
         assert mq <= self.mq
         T = B * mq
         self._note_ctx(max(num_tokens) + self._async_lookahead())
         sample = temps is not None and any(t > 0 for t in temps)
+        filt = sample and filters is not None
         if sample:
             self._ensure_stochastic()
             if self.d_tree_logits is None:
@@ -869,13 +923,15 @@ class ModelRunner:
             self.d_ids[:T].copy_(forks.reshape(-1))
             if sample:
                 self._upload(self.d_temps, list(temps), torch.float32)
+            if filt:
+                self._upload_filters(filters)
 
         def all_steps():                 # the K tree steps in ONE hipGraph (each step has its own static metadata rows)
             for d in range(K):
-                self._body_tree(B, d, sample, mq)
+                self._body_tree(B, d, sample, mq, filt)
 
         stage()
-        key = ("tree_s" if sample else "tree", B, mq)
+        key = (("tree_sf" if filt else "tree_s") if sample else "tree", B, mq)
         if self._launch(key, all_steps) == "captured":
             self.d_ids[:T].copy_(forks.reshape(-1))      # the eager warm-up consumed the inputs
             self.graphs[(*key, self._ctx_hint)].replay()

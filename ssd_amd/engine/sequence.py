@@ -40,6 +40,7 @@ class Sequence:
         self.first_token_streamed: int | None = None
         self.temperature = sp.temperature
         self.draft_temperature = sp.draft_temperature
+        self.top_k, self.top_p, self.min_p = sp.top_k, sp.top_p, sp.min_p       # logit filter (0 / 1.0 / 0.0 = off)
         self.max_new_tokens = sp.max_new_tokens
         self.ignore_eos = sp.ignore_eos
         # EAGLE-3 (reference sequence.py:23-24,47-51): the target activation that conditions the next recovery token, and
@@ -54,6 +55,10 @@ class Sequence:
 
     def __getitem__(self, key):
         return self.token_ids[key]
+
+    @property
+    def has_filter(self) -> bool:
+        return self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0
 
     @property
     def is_finished(self) -> bool:

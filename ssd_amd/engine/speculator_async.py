@@ -58,19 +58,24 @@ class AsyncLink:
         if pump is not None and not (eagle_acts is None and getattr(self.tx, "defer_prefill", False)):
             pump()      # (co-located on a GPU: deferred to the first speculation request, engine/llm_engine.py)
 
-    def speculate(self, keys, num_tokens, block_tables, temps, want_logits: bool = False, eagle=None):
+    def speculate(self, keys, num_tokens, block_tables, temps, want_logits: bool = False, eagle=None, filters=None):
         """-> (hits, tokens, logits_q or None).  logits_q bf16 [B, K, V] is requested only when some temperature is
-        > 0 (FLAG_WANT_LOGITS) and reaches every TP rank: each rank runs the ratio test on its own device."""
+        > 0 (FLAG_WANT_LOGITS) and reaches every TP rank: each rank runs the ratio test on its own device.
+        filters: None, or (top_k [B], top_p [B], min_p [B]) when some sequence has a logit filter (FLAG_FILTER)."""
         B, K = len(keys), self.K
         resp, lq = None, None
         V = self.config.hf_config.vocab_size
         if self.is_head:
             flags = P.FLAG_WANT_LOGITS if want_logits else 0
+            fkw = {}
+            if filters is not None:
+                flags |= P.FLAG_FILTER
+                fkw = {"filters": filters}
             if eagle is not None:       # (extend_counts [B], extend_ids [B][K], acts [B, K+1, A])
-                payload = P.pack_speculate(keys, num_tokens, block_tables, temps, self.max_blocks, eagle[0], eagle[1])
+                payload = P.pack_speculate(keys, num_tokens, block_tables, temps, self.max_blocks, eagle[0], eagle[1], **fkw)
                 flags |= P.FLAG_EAGLE
             else:
-                payload = P.pack_speculate(keys, num_tokens, block_tables, temps, self.max_blocks)
+                payload = P.pack_speculate(keys, num_tokens, block_tables, temps, self.max_blocks, **fkw)
             self.tx.send_ints([P.CMD_SPECULATE, B, len(payload), flags])
             self.tx.send_ints(payload)
             if eagle is not None:
@@ -139,7 +144,11 @@ class SpeculatorAsync(SpeculatorBase):
                     acts[i, :n] = seq.extend_eagle_acts[:n]
                 acts[i, K] = seq.last_target_hidden_state
             eagle = (counts, ext_ids, acts)
-        hits, tokens, logits_q = self.link.speculate(keys, nts, tables, temps, want_logits=want, eagle=eagle)
+        # logit filters travel only when some sequence has one, and never to an EAGLE-3 draft (greedy: only the target truncates)
+        fkw = {}
+        if eagle is None and any(getattr(s, "has_filter", False) for s in seqs):
+            fkw = {"filters": ([s.top_k for s in seqs], [s.top_p for s in seqs], [s.min_p for s in seqs])}
+        hits, tokens, logits_q = self.link.speculate(keys, nts, tables, temps, want_logits=want, eagle=eagle, **fkw)
         rows = []
         for seq, toks in zip(seqs, tokens):
             rows.append([seq.recovery_token_id] + toks)
