@@ -186,6 +186,16 @@ class LLMEngine:
                 if runner is not None and not getattr(runner, "supports_logit_filters", False):
                     raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no logit filter "
                                      f"(requested: {', '.join(active)})")
+        active = sampling_params.active_penalties if sampling_params is not None else []
+        if active:      # penalties and logit_bias need a runner that adjusts the raw rows from the token history (the HIP runners do)
+            for runner in (getattr(self, "model_runner", None), self.draft_runner):
+                if runner is not None and not getattr(runner, "supports_logit_penalties", False):
+                    raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no logit penalties "
+                                     f"(requested: {', '.join(active)})")
+                cap = getattr(runner, "PENALTY_MAX_BIAS", None)
+                if cap is not None and sampling_params.logit_bias and len(sampling_params.logit_bias) > cap:
+                    raise ValueError(f"logit_bias has {len(sampling_params.logit_bias)} entries: the history table of "
+                                     f"{type(runner).__name__} holds at most {cap} biased ids beside the sequence's own tokens")
         self.scheduler.add(Sequence(prompt, sampling_params))
 
     def step(self, step: InferenceStep):

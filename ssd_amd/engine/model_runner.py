@@ -14,11 +14,13 @@ Re-designed for this hardware rather than translated:
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import filter_ops as HF
+from ssd_amd.hip import penalty_ops as HP
 from ssd_amd.hip.lib import load_library
 from ssd_amd.model import HipDecoder, AttnMeta
 from ssd_amd.model_config import ModelConfig
@@ -31,6 +33,8 @@ class ModelRunner:
     PREFILL_GRAPHS = 4              # prefill shapes kept as hipGraphs
     PREFILL_GRAPH_MAX_T = 1024      # longer prefills are GPU-bound by far: launch overhead does not matter
     supports_logit_filters = True   # top_k / top_p / min_p (csrc/filter.hip); LLMEngine.add_request refuses them on runners without it
+    supports_logit_penalties = True # repetition / presence / frequency penalty, logit_bias (csrc/penalty.hip); refused likewise
+    PENALTY_MAX_BIAS = 1024         # logit_bias entries one request may carry: the history table holds max_model_len + this many ids
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
                  tp_size: int = 1, tp_group=None, model_path: str | None = None, weights_seed: int = 0,
@@ -363,13 +367,17 @@ class ModelRunner:
         are keyed by its power-of-two bucket because the attention decomposition is fixed at capture."""
         self._ctx_hint = HipDecoder.ctx_bucket(max_ctx)
 
-    def _body_decode(self, B: int, chain: bool, head: bool = True, sample: bool = False, filt: bool = False) -> None:
+    def _body_decode(self, B: int, chain: bool, head: bool = True, sample: bool = False, filt: bool = False, pen: bool = False) -> None:
         self.model.forward(self.d_ids, self.d_pos, B, self._meta("decode", B))
         if not head:        # KV deposit only (the (K+1)-th draft forward, speculator_sync.py:55-56): no LM head / sampling
             return
         self.model.compute_logits(B)
-        if sample:          # temperature > 0: keep logits_q for the ratio test and draw with the Gumbel-max sampler
+        if pen:             # on the raw logits, in front of everything below; a chain step also sees the chain's own tokens so far
             lg = self.model.full_logits(B)
+            self._penalize(lg, B, 1, "chain" if chain else None)
+        if sample:          # temperature > 0: keep logits_q for the ratio test and draw with the Gumbel-max sampler
+            if not pen:
+                lg = self.model.full_logits(B)
             V = self.cfg.vocab_size
             if filt:        # before anything reads the rows: the stored logits_q, the boost rows and the draw see the truncated row
                 self._filter(lg, B, 1)
@@ -384,6 +392,8 @@ class ModelRunner:
             else:
                 H.sample_rows(lg, V, B, V, self.d_temps, 1, self.d_rng, 1, self.d_next)
             H.rng_advance(self.d_rng)
+        elif pen:           # greedy over the adjusted rows: the LM head's argmax candidates predate the adjustment
+            H.argmax_rows(lg, self.cfg.vocab_size, B, self.cfg.vocab_size, self.d_next)
         elif chain and self.model.has_argmax_parts(B):
             # argmax from the LM head's candidates + the chain advance: one launch
             self.model.argmax_advance(B, self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
@@ -395,14 +405,20 @@ class ModelRunner:
             H.draft_advance(self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                             self.block_size, self.d_spec, self.K, self.d_step, B)
 
-    def _body_verify(self, B: int, greedy_tail: bool, logits_q=None, filt: bool = False) -> None:
+    def _body_verify(self, B: int, greedy_tail: bool, logits_q=None, filt: bool = False, pen: bool = False) -> None:
         T = B * (self.K + 1)
         self.model.forward(self.d_ids, self.d_pos, T, self._meta("verify", B))
         self.model.compute_logits(T)
+        if pen:             # row j with the history autoregressive decoding would have had there: the table + inputs 1..j of the round
+            lg = self.model.full_logits(T)
+            self._penalize(lg, T, self.K + 1, "prefix")
         if logits_q is not None:     # temperature > 0: ratio acceptance + residual resampling (utils/verify.py:50-167)
             K, V = self.K, self.cfg.vocab_size
-            lg = self.model.full_logits(T)
-            self.model.argmax(T, self.d_next)
+            if pen:
+                H.argmax_rows(lg, V, T, V, self.d_next)
+            else:
+                lg = self.model.full_logits(T)
+                self.model.argmax(T, self.d_next)
             if filt:        # the target's p only: logits_q was truncated once, where the draft sampled from it
                 self._filter(lg, T, K + 1)
             H.row_lse(lg, V, T, V, self.d_temps, K + 1, self.d_lse_p)
@@ -416,7 +432,10 @@ class ModelRunner:
                            boost_idx_q=self.d_boost if boost else None, **boost)
             H.rng_advance(self.d_rng)
             return
-        if greedy_tail and self.K + 1 <= 16 and self.model.has_argmax_parts(T):
+        if greedy_tail and pen:
+            H.argmax_rows(lg, self.cfg.vocab_size, T, self.cfg.vocab_size, self.d_next)
+            H.verify_greedy(self.d_next, self.d_ids, B, self.K, self.d_accept, self.d_recovery, self.d_packed)
+        elif greedy_tail and self.K + 1 <= 16 and self.model.has_argmax_parts(T):
             # LM head -> [argmax from its candidates + accept / reject] : the verify graph's tail is two launches
             self.model.argmax_verify(B, self.K, self.d_ids, self.d_next, self.d_accept, self.d_recovery, self.d_packed)
         elif greedy_tail:
@@ -506,16 +525,23 @@ class ModelRunner:
             return self.model.full_logits(T)
         self._prepare_decode(seqs)
         temps = self._seq_temps(seqs)
+        pen = self._seq_penalties(seqs)
+        if pen:
+            self._upload_penalties(seqs)
         if any(t > 0 for t in temps):       # autoregressive sampling (AutoRegressiveStep at temperature > 0)
             self._ensure_stochastic()
             self._upload(self.d_temps, temps, torch.float32)
             filters = self._seq_filters(seqs)
             if filters is not None:
                 self._upload_filters(filters)
-            key = ("decode_sf" if filters is not None else "decode_s", B)
-            if self._launch(key, lambda: self._body_decode(B, False, sample=True, filt=filters is not None)) == "captured":
+            key = (("decode_sf" if filters is not None else "decode_s") + ("_p" if pen else ""), B)
+            if self._launch(key, lambda: self._body_decode(B, False, sample=True, filt=filters is not None, pen=pen)) == "captured":
                 self._prepare_decode(seqs)
                 self.graphs[(*key, self._ctx_hint)].replay()
+        elif pen:                           # greedy with penalties: the full-logits argmax tail
+            if self._launch(("decode_p", B), lambda: self._body_decode(B, False, pen=True)) == "captured":
+                self._prepare_decode(seqs)
+                self.graphs[("decode_p", B, self._ctx_hint)].replay()
         elif self._launch(("decode", B), lambda: self._body_decode(B, False)) == "captured":
             self._prepare_decode(seqs)
             self.graphs[("decode", B, self._ctx_hint)].replay()
@@ -565,13 +591,83 @@ class ModelRunner:
         V = self.cfg.vocab_size
         HF.filter_rows(lg, V, rows, V, self.d_temps, self.d_top_k, self.d_top_p, self.d_min_p, rows_per_param)
 
+    @staticmethod
+    def _seq_penalties(seqs) -> bool:
+        """Some sequence of the batch has a penalty or a logit bias (otherwise nothing is uploaded or launched)."""
+        return any(getattr(s, "has_penalty", False) for s in seqs)
+
+    def _ensure_penalty(self) -> None:
+        """Device tables of csrc/penalty.hip beside d_top_k, with their pinned staging (allocated on first use)."""
+        if hasattr(self, "d_pen_ids"):
+            return
+        assert self.K + 1 <= HP.MAX_EXTRA + 1, "speculate_k exceeds SSD_PENALTY_MAX_EXTRA"
+        B, L = self.seq_cap, self.config.max_model_len + self.PENALTY_MAX_BIAS
+        dev = dict(device=self.device)
+        self.pen_tab_ld = L
+        self.d_pen_ids = torch.zeros(B, L, dtype=torch.int32, **dev)        # unique token ids of each sequence's history
+        self.d_pen_cnt = torch.zeros(B, L, dtype=torch.int32, **dev)        # (output count << 1) | in prompt
+        self.d_pen_bias = torch.zeros(B, L, dtype=torch.float32, **dev)
+        self.d_pen_len = torch.zeros(B, dtype=torch.int32, **dev)
+        self.d_pen_par = torch.zeros(3, B, dtype=torch.float32, **dev)      # rows: repetition, presence, frequency
+        self._pen_stage = {}
+
+    def _upload_penalties(self, seqs, back: int = 0) -> None:
+        """Stage every sequence's history table and parameters.  back: lookahead entries at the end of token_ids that are not
+        history (the K speculated tokens under verification: the kernel reads those from the round's inputs, row by row)."""
+        self._ensure_penalty()
+        st = self._pen_stage.get(self._stage_set)
+        if st is None:
+            dsts = (self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.d_pen_len, self.d_pen_par)
+            pinned = [torch.zeros(d.shape, dtype=d.dtype).pin_memory() for d in dsts]
+            st = self._pen_stage[self._stage_set] = (pinned, [t.numpy() for t in pinned])
+        pinned, (ids, cnt, bias, lens, par) = st
+        B, L = len(seqs), self.pen_tab_ld
+        for b, s in enumerate(seqs):
+            if not getattr(s, "has_penalty", False):
+                lens[b], par[0, b], par[1, b], par[2, b] = 0, 1.0, 0.0, 0.0
+                continue
+            tab = s.penalty_table(len(s.token_ids) - back)
+            n = len(tab)
+            if n > L:
+                raise ValueError(f"the history of sequence {s.seq_id} ({n} distinct token and logit_bias ids) does not fit the penalty "
+                                 f"table of {L} entries (max_model_len + {self.PENALTY_MAX_BIAS})")
+            if n:
+                vals = np.array(list(tab.values()), dtype=np.float64)
+                ids[b, :n] = np.clip(np.fromiter(tab.keys(), dtype=np.int64, count=n), -1, 2 ** 31 - 1)
+                cnt[b, :n] = (vals[:, 0].astype(np.int64) << 1) | vals[:, 1].astype(np.int64)
+                bias[b, :n] = vals[:, 2]
+            lens[b], par[0, b], par[1, b], par[2, b] = n, s.repetition_penalty, s.presence_penalty, s.frequency_penalty
+        for d, h in zip((self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.d_pen_len), pinned):
+            d[:B].copy_(h[:B], non_blocking=True)
+        self.d_pen_par.copy_(pinned[4], non_blocking=True)
+
+    def _penalize(self, lg: torch.Tensor, rows: int, rows_per_seq: int, form: str | None) -> None:
+        """Adjust `rows` raw logit rows in place with the uploaded tables.  form None: the table alone; "prefix": row j of a sequence
+        also sees inputs 1..j of its K+1 verify inputs (d_ids); "chain": every row also sees the d_step tokens its draft chain has
+        produced so far (d_spec).  Rows of sequences without penalties come back untouched."""
+        V, K = self.cfg.vocab_size, self.K
+        extra = dict(extra=self.d_ids, extra_ld=K + 1) if form == "prefix" else \
+            dict(extra=self.d_spec, extra_ld=K + 1, extra_n=self.d_step) if form == "chain" else {}
+        HP.penalize_rows(lg, V, rows, V, rows_per_seq, self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.pen_tab_ld, self.d_pen_len,
+                         self.d_pen_par[0], self.d_pen_par[1], self.d_pen_par[2], **extra)
+
     def _sample_or_argmax(self, seqs, B: int) -> None:
         temps = self._seq_temps(seqs)
+        pen = not self.is_draft and self._seq_penalties(seqs)      # (a draft's prefill token is never used)
+        if pen:             # the prefill's first token: its history is the prompt
+            self._upload_penalties(seqs)
+            V = self.cfg.vocab_size
+            lg = self.model.full_logits(B)
+            self._penalize(lg, B, 1, None)
+            if not any(t > 0 for t in temps):
+                H.argmax_rows(lg, V, B, V, self.d_next)
+                return
         if any(t > 0 for t in temps):
             self._ensure_stochastic()
             self._upload(self.d_temps, temps, torch.float32)
             V = self.cfg.vocab_size
-            lg = self.model.full_logits(B)
+            if not pen:
+                lg = self.model.full_logits(B)
             filters = self._seq_filters(seqs)
             if filters is not None:
                 self._upload_filters(filters)
@@ -600,7 +696,8 @@ class ModelRunner:
         sample = any(t > 0 for t in temps)
         filters = self._seq_filters(seqs) if sample else None
         filt = filters is not None
-        key = (("decode_chain_sf" if filt else "decode_chain_s") if sample else "decode_chain", B)
+        pen = self._seq_penalties(seqs)     # the draft is penalised like the target, or it proposes what the target will reject
+        key = ((("decode_chain_sf" if filt else "decode_chain_s") if sample else "decode_chain") + ("_p" if pen else ""), B)
         if sample:
             self._ensure_stochastic()
 
@@ -612,10 +709,12 @@ class ModelRunner:
                 self._upload(self.d_temps, temps, torch.float32)
             if filt:
                 self._upload_filters(filters)
+            if pen:
+                self._upload_penalties(seqs)
 
         def chain():                     # all K forwards in ONE hipGraph: no host gap between them
             for _ in range(K):
-                self._body_decode(B, True, sample=sample, filt=filt)
+                self._body_decode(B, True, sample=sample, filt=filt, pen=pen)
 
         stage()
         if self._launch(key, chain) == "captured":
@@ -653,7 +752,8 @@ class ModelRunner:
         stochastic = temps_q is not None
         filters = self._seq_filters(seqs) if stochastic else None
         filt = filters is not None
-        key = (("verify_sf" if filt else "verify_s") if stochastic else "verify", B)
+        pen = self._seq_penalties(seqs)
+        key = ((("verify_sf" if filt else "verify_s") if stochastic else "verify") + ("_p" if pen else ""), B)
         if stochastic:
             self._ensure_stochastic()
             if logits_q is None:        # greedy draft under a sampling target: q is one-hot, its logits are never read
@@ -662,7 +762,7 @@ class ModelRunner:
                 logits_q = self._lq_dummy[:B]
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
             if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):
-                self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in ("verify_s", "verify_sf")}   # pointer is baked in the graph
+                self.graphs = {k: v for k, v in self.graphs.items() if not k[0].startswith("verify_s")}   # pointer is baked in the graph
             self._lq_ptr = logits_q.data_ptr()
 
         def stage():
@@ -674,9 +774,11 @@ class ModelRunner:
                 self._upload(self.d_ratio, [int(r) for r in ratio_rows], torch.int32)
             if filt:
                 self._upload_filters(filters)
+            if pen:             # token_ids ends in the K speculated positions: row j reads those from the inputs
+                self._upload_penalties(seqs, back=K)
 
         stage()
-        if self._launch(key, lambda: self._body_verify(B, True, logits_q=logits_q, filt=filt)) == "captured":
+        if self._launch(key, lambda: self._body_verify(B, True, logits_q=logits_q, filt=filt, pen=pen)) == "captured":
             stage()
             self.graphs[(*key, self._ctx_hint)].replay()
         self._log_margins(B * (K + 1), [(s.seq_id, s.num_tokens - (K + 1) + j + 1) for s in seqs for j in range(K + 1)])

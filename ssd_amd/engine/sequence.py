@@ -41,6 +41,17 @@ class Sequence:
         self.temperature = sp.temperature
         self.draft_temperature = sp.draft_temperature
         self.top_k, self.top_p, self.min_p = sp.top_k, sp.top_p, sp.min_p       # logit filter (0 / 1.0 / 0.0 = off)
+        # penalties and logit bias (include/ssd_hip_penalty.h; 1.0 / 0.0 / 0.0 / None = off)
+        self.repetition_penalty, self.presence_penalty = float(sp.repetition_penalty), float(sp.presence_penalty)
+        self.frequency_penalty = float(sp.frequency_penalty)
+        self.logit_bias = {int(t): float(v) for t, v in sp.logit_bias.items()} if sp.logit_bias else None
+        # the sparse history behind them: token id -> [output count, in prompt, bias], kept for token_ids[:_pen_n].  "Prompt" is the
+        # request's own prompt for good: a preemption turns completions into prompt for the scheduler, not for the penalties
+        self.num_request_prompt_tokens = self.num_tokens
+        self._pen: dict[int, list] | None = None
+        self._pen_n = 0
+        if self.has_penalty:
+            self._pen = {t: [0, False, v] for t, v in (self.logit_bias or {}).items()}
         self.max_new_tokens = sp.max_new_tokens
         self.ignore_eos = sp.ignore_eos
         # EAGLE-3 (reference sequence.py:23-24,47-51): the target activation that conditions the next recovery token, and
@@ -59,6 +70,47 @@ class Sequence:
     @property
     def has_filter(self) -> bool:
         return self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0
+
+    @property
+    def has_penalty(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+                or bool(self.logit_bias))
+
+    def penalty_table(self, upto: int | None = None) -> dict[int, list]:
+        """token id -> [occurrences after the request's prompt, occurs in the prompt, bias] over token_ids[:upto] (default: all of
+        them) plus the biased ids; placeholders (negative ids) are not history.  Kept incrementally: a call accounts for the tokens
+        appended since the last one and takes back those beyond `upto`; `restore` takes back what it cuts off.  Only sequences with
+        has_penalty keep one."""
+        assert self._pen is not None, "penalty_table() of a sequence without penalties"
+        self._pen_sync(len(self.token_ids) if upto is None else upto)
+        return self._pen
+
+    def _pen_sync(self, upto: int) -> None:
+        pen, ids, P = self._pen, self.token_ids, self.num_request_prompt_tokens
+        assert 0 <= upto <= len(ids)
+        if upto < self._pen_n and upto < P:         # cutting into the prompt: another occurrence may remain, recount
+            self._pen = pen = {t: [0, False, v] for t, v in (self.logit_bias or {}).items()}
+            self._pen_n = 0
+        for i in range(self._pen_n, upto):
+            t = ids[i]
+            if t < 0:
+                continue
+            e = pen.get(t)
+            if e is None:
+                e = pen[t] = [0, False, 0.0]
+            if i < P:
+                e[1] = True
+            else:
+                e[0] += 1
+        for i in range(upto, self._pen_n):
+            t = ids[i]
+            if t < 0:
+                continue
+            e = pen[t]
+            e[0] -= 1
+            if e[0] == 0 and not e[1] and not (self.logit_bias and t in self.logit_bias):
+                del pen[t]
+        self._pen_n = upto
 
     @property
     def is_finished(self) -> bool:
@@ -113,4 +165,6 @@ class Sequence:
 
     def restore(self, snap) -> None:
         n, self.num_tokens, self.last_token, self.num_draft_cached_tokens, self.num_cached_tokens = snap
+        if self._pen is not None and self._pen_n > n:       # the history forgets the lookahead tokens before they go
+            self._pen_sync(n)
         del self.token_ids[n:]

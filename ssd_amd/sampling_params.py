@@ -1,6 +1,12 @@
 """SamplingParams -- the reference's fields and defaults (ssd/sampling_params.py:4-9) plus the truncation every other LLM.generate offers:
-top_k / top_p / min_p, applied in the Hugging Face order after the temperature (include/ssd_hip_filter.h has the exact semantics)."""
+top_k / top_p / min_p, applied in the Hugging Face order after the temperature (include/ssd_hip_filter.h has the exact semantics), and,
+before the temperature, repetition / presence / frequency penalties and logit bias (include/ssd_hip_penalty.h)."""
+import math
 from dataclasses import dataclass
+
+
+def _is_real(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
 @dataclass
@@ -12,6 +18,10 @@ class SamplingParams:
     top_k: int = 0              # keep the k most probable tokens (ties at the k-th kept); 0 = off
     top_p: float = 1.0          # keep the smallest set of most probable tokens whose mass reaches top_p; 1.0 = off
     min_p: float = 0.0          # keep tokens whose probability is at least min_p times the largest; 0.0 = off
+    repetition_penalty: float = 1.0     # logits of tokens in the prompt or the output: divided by it if >= 0, multiplied if < 0; 1.0 = off
+    presence_penalty: float = 0.0       # subtracted once from the logit of every token already in the output; 0.0 = off
+    frequency_penalty: float = 0.0      # subtracted per occurrence in the output; 0.0 = off
+    logit_bias: dict | None = None      # token id -> value in [-100, 100] added to that token's logit; None = off
 
     def __post_init__(self):
         if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or self.top_k < 0:
@@ -20,6 +30,26 @@ class SamplingParams:
             raise ValueError(f"top_p must be in (0, 1] (1 = off), got {self.top_p!r}")
         if not (0.0 <= self.min_p <= 1.0):
             raise ValueError(f"min_p must be in [0, 1] (0 = off), got {self.min_p!r}")
+        if not _is_real(self.repetition_penalty) or not self.repetition_penalty > 0.0:
+            raise ValueError(f"repetition_penalty must be finite and > 0 (1 = off), got {self.repetition_penalty!r}")
+        if not _is_real(self.presence_penalty):
+            raise ValueError(f"presence_penalty must be finite (0 = off), got {self.presence_penalty!r}")
+        if not _is_real(self.frequency_penalty):
+            raise ValueError(f"frequency_penalty must be finite (0 = off), got {self.frequency_penalty!r}")
+        if self.logit_bias is not None:
+            if not isinstance(self.logit_bias, dict):
+                raise ValueError(f"logit_bias must be a dict of token id -> bias or None, got {self.logit_bias!r}")
+            for t, v in self.logit_bias.items():
+                if isinstance(t, bool) or not isinstance(t, int) or t < 0:
+                    raise ValueError(f"logit_bias keys must be integers >= 0, got {t!r}")
+                if not _is_real(v) or not -100.0 <= v <= 100.0:
+                    raise ValueError(f"logit_bias values must be finite and within [-100, 100], got {v!r} for token {t}")
+
+    @property
+    def active_penalties(self) -> list[str]:
+        """Names of the penalty parameters that are switched on."""
+        return [n for n, on in (("repetition_penalty", self.repetition_penalty != 1.0), ("presence_penalty", self.presence_penalty != 0.0),
+                                ("frequency_penalty", self.frequency_penalty != 0.0), ("logit_bias", bool(self.logit_bias))) if on]
 
     @property
     def active_filters(self) -> list[str]:
