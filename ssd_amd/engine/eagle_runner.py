@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import torch
 
-from ssd_amd.engine.model_runner import ModelRunner
+from ssd_amd.engine.model_runner import GREEDY, ModelRunner, Sampling
 from ssd_amd.hip import ops as H
 
 
@@ -95,10 +95,7 @@ class EagleDraftRunner(ModelRunner):
                 H.draft_advance(self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                                 self.block_size, self.d_spec, self.K, self.d_step, B)
 
-        stage()
-        if self._launch(("eagle_chain", B), chain) == "captured":
-            stage()
-            self.graphs[("eagle_chain", B, self._ctx_hint)].replay()
+        self._run_graph(("eagle_chain", B), stage, chain)
         return self.d_spec[:B, 1:].clone()
 
     def jit_acts(self, B: int) -> torch.Tensor:
@@ -165,12 +162,12 @@ class EagleDraftRunner(ModelRunner):
         return self.d_forks[:B].clone()
 
     # ---- tree: branch i starts from the glue prenorm of its position j_i, then conditions on its own previous step ----
-    def _body_tree(self, B: int, d: int, sample: bool = False, mq: int | None = None, filt: bool = False) -> None:
+    def _body_tree(self, B: int, d: int, how: Sampling = GREEDY, mq: int | None = None) -> None:
         m = self.model
         T = B * (mq or self.mq)
         if d == 0:
             torch.index_select(self.d_glue_pre, 0, self.d_cond_idx[:T], out=m.buf_cond[:T])
-        super()._body_tree(B, d, sample, mq, filt)      # (greedy-only: sample and filt are always False here)
+        super()._body_tree(B, d, how, mq)       # (greedy-only: `how` is always GREEDY here)
         self.d_tree_acts[:T, d].copy_(m.buf_pre[:T])
         m.buf_cond[:T].copy_(m.buf_pre[:T])
 

@@ -14,6 +14,8 @@ Re-designed for this hardware rather than translated:
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -27,6 +29,27 @@ from ssd_amd.model_config import ModelConfig
 from ssd_amd import weights as W
 from ssd_amd.utils.graphs import capture
 from ssd_amd.engine.async_proto import to_device
+
+
+class Sampling(NamedTuple):
+    """How one batch turns logits into tokens; it selects the graph (suffix) and the tail every body runs (_rows, _draw, _greedy)."""
+    sample: bool = False    # some temperature > 0: draw with the Gumbel-max sampler (a verify: ratio acceptance)
+    filt: bool = False      # some sampled sequence has top_k / top_p / min_p: truncate the rows first
+    pen: bool = False       # some sequence has a penalty or a logit bias: adjust the raw rows in front of everything else
+
+    @property
+    def suffix(self) -> str:
+        """What a graph's name carries behind "decode" / "decode_chain" / "verify" / "tree"."""
+        return ("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "")
+
+    @classmethod
+    def explicit(cls, temps, filters) -> "Sampling":
+        """The draft server's requests carry arrays, not sequences, and are not penalised."""
+        sample = temps is not None and any(t > 0 for t in temps)
+        return cls(sample, sample and filters is not None)
+
+
+GREEDY = Sampling()
 
 
 class ModelRunner:
@@ -367,59 +390,72 @@ class ModelRunner:
         are keyed by its power-of-two bucket because the attention decomposition is fixed at capture."""
         self._ctx_hint = HipDecoder.ctx_bucket(max_ctx)
 
-    def _body_decode(self, B: int, chain: bool, head: bool = True, sample: bool = False, filt: bool = False, pen: bool = False) -> None:
+    # The tail "logits -> (penalise) -> (truncate) -> draw or argmax" of every body, in three pieces.  Bodies differ in the rows per
+    # parameter set (1, K + 1, the tree width), the RNG salt (1 decode and chain, 2 ratio verify, 3 prefill, 4 tree), the penalty
+    # form and what is kept of the sampled rows -- and in the fused greedy launches they use when nothing adjusts the rows.
+    def _rows(self, n: int, how: Sampling, rows_per_seq: int = 1, form: str | None = None):
+        """The n raw logit rows of the last compute_logits, penalised when asked (on the raw logits, in front of everything else);
+        None on the plain greedy path, which reads the LM head's argmax candidates instead."""
+        if not (how.sample or how.pen):
+            return None
+        lg = self.model.full_logits(n)
+        if how.pen:
+            self._penalize(lg, n, rows_per_seq, form)
+        return lg
+
+    def _draw(self, lg: torch.Tensor, n: int, how: Sampling, rows_per_param: int, salt: int, keep=None, boost: bool = False) -> None:
+        """Temperature > 0: truncate, keep the rows for the ratio test (keep = (logits_q table, step): what is stored, the boost rows
+        and the draw all see the truncated row), draw d_next with the Gumbel-max sampler, move the RNG on."""
+        V = self.cfg.vocab_size
+        if how.filt:
+            self._filter(lg, n, rows_per_param)
+        if keep is not None:
+            H.store_step_rows(lg, V, keep[0], n, V, self.K, keep[1])
+        kw = {}
+        if boost and self.sx is not None:
+            # the async draft samples with is_tree=True (reference draft_runner.py:172 -> sampler.py:29-31): under sampler_x its
+            # tokens come from the rescaled distribution, the q that verify() divides by
+            H.topk_rows(lg, V, n, V, self.sx_k, self.d_boost)
+            kw = dict(boost_idx=self.d_boost, boost_k=self.sx_k, boost_x=self.sx)
+        H.sample_rows(lg, V, n, V, self.d_temps, rows_per_param, self.d_rng, salt, self.d_next, **kw)
+        H.rng_advance(self.d_rng)
+
+    def _greedy(self, lg, n: int, how: Sampling) -> None:
+        """d_next = argmax: over the adjusted rows when they were penalised (the LM head's candidates predate the adjustment)."""
+        if how.pen:
+            H.argmax_rows(lg, self.cfg.vocab_size, n, self.cfg.vocab_size, self.d_next)
+        else:
+            self.model.argmax(n, self.d_next)
+
+    def _body_decode(self, B: int, chain: bool, head: bool = True, how: Sampling = GREEDY) -> None:
         self.model.forward(self.d_ids, self.d_pos, B, self._meta("decode", B))
         if not head:        # KV deposit only (the (K+1)-th draft forward, speculator_sync.py:55-56): no LM head / sampling
             return
         self.model.compute_logits(B)
-        if pen:             # on the raw logits, in front of everything below; a chain step also sees the chain's own tokens so far
-            lg = self.model.full_logits(B)
-            self._penalize(lg, B, 1, "chain" if chain else None)
-        if sample:          # temperature > 0: keep logits_q for the ratio test and draw with the Gumbel-max sampler
-            if not pen:
-                lg = self.model.full_logits(B)
-            V = self.cfg.vocab_size
-            if filt:        # before anything reads the rows: the stored logits_q, the boost rows and the draw see the truncated row
-                self._filter(lg, B, 1)
-            if chain:
-                H.store_step_rows(lg, V, self.d_logits_q, B, V, self.K, self.d_step)
-            if chain and self.is_draft and self.sx is not None:
-                # the async draft's JIT chain samples with is_tree=True (reference draft_runner.py:172 -> sampler.py:29-31):
-                # under sampler_x its tokens come from the rescaled distribution, the q that verify() divides by
-                H.topk_rows(lg, V, B, V, self.sx_k, self.d_boost)
-                H.sample_rows(lg, V, B, V, self.d_temps, 1, self.d_rng, 1, self.d_next, boost_idx=self.d_boost, boost_k=self.sx_k,
-                              boost_x=self.sx)
-            else:
-                H.sample_rows(lg, V, B, V, self.d_temps, 1, self.d_rng, 1, self.d_next)
-            H.rng_advance(self.d_rng)
-        elif pen:           # greedy over the adjusted rows: the LM head's argmax candidates predate the adjustment
-            H.argmax_rows(lg, self.cfg.vocab_size, B, self.cfg.vocab_size, self.d_next)
-        elif chain and self.model.has_argmax_parts(B):
+        lg = self._rows(B, how, 1, "chain" if chain else None)      # a chain step also sees the chain's own tokens so far
+        if how.sample:
+            self._draw(lg, B, how, 1, 1, keep=(self.d_logits_q, self.d_step) if chain else None, boost=chain and self.is_draft)
+        elif chain and not how.pen and self.model.has_argmax_parts(B):
             # argmax from the LM head's candidates + the chain advance: one launch
             self.model.argmax_advance(B, self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                                       self.block_size, self.d_spec, self.K, self.d_step)
             return
         else:
-            self.model.argmax(B, self.d_next)
+            self._greedy(lg, B, how)
         if chain:
             H.draft_advance(self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                             self.block_size, self.d_spec, self.K, self.d_step, B)
 
-    def _body_verify(self, B: int, greedy_tail: bool, logits_q=None, filt: bool = False, pen: bool = False) -> None:
-        T = B * (self.K + 1)
+    def _body_verify(self, B: int, greedy_tail: bool, logits_q=None, how: Sampling = GREEDY) -> None:
+        K, V = self.K, self.cfg.vocab_size
+        T = B * (K + 1)
         self.model.forward(self.d_ids, self.d_pos, T, self._meta("verify", B))
         self.model.compute_logits(T)
-        if pen:             # row j with the history autoregressive decoding would have had there: the table + inputs 1..j of the round
-            lg = self.model.full_logits(T)
-            self._penalize(lg, T, self.K + 1, "prefix")
-        if logits_q is not None:     # temperature > 0: ratio acceptance + residual resampling (utils/verify.py:50-167)
-            K, V = self.K, self.cfg.vocab_size
-            if pen:
-                H.argmax_rows(lg, V, T, V, self.d_next)
-            else:
-                lg = self.model.full_logits(T)
-                self.model.argmax(T, self.d_next)
-            if filt:        # the target's p only: logits_q was truncated once, where the draft sampled from it
+        # penalised: row j with the history autoregressive decoding would have had there, the table + inputs 1..j of the round
+        lg = self._rows(T, how, K + 1, "prefix")
+        if how.sample:      # temperature > 0: ratio acceptance + residual resampling (utils/verify.py:50-167)
+            self._greedy(lg, T, how)
+            if how.filt:    # the target's p only: logits_q was truncated once, where the draft sampled from it
                 self._filter(lg, T, K + 1)
             H.row_lse(lg, V, T, V, self.d_temps, K + 1, self.d_lse_p)
             boost = {}
@@ -431,16 +467,12 @@ class ModelRunner:
                            self.d_temps_q, self.d_ratio, self.d_rng, 2, self.d_accept, self.d_recovery, self.d_packed,
                            boost_idx_q=self.d_boost if boost else None, **boost)
             H.rng_advance(self.d_rng)
-            return
-        if greedy_tail and pen:
-            H.argmax_rows(lg, self.cfg.vocab_size, T, self.cfg.vocab_size, self.d_next)
-            H.verify_greedy(self.d_next, self.d_ids, B, self.K, self.d_accept, self.d_recovery, self.d_packed)
-        elif greedy_tail and self.K + 1 <= 16 and self.model.has_argmax_parts(T):
+        elif greedy_tail and not how.pen and K + 1 <= 16 and self.model.has_argmax_parts(T):
             # LM head -> [argmax from its candidates + accept / reject] : the verify graph's tail is two launches
-            self.model.argmax_verify(B, self.K, self.d_ids, self.d_next, self.d_accept, self.d_recovery, self.d_packed)
+            self.model.argmax_verify(B, K, self.d_ids, self.d_next, self.d_accept, self.d_recovery, self.d_packed)
         elif greedy_tail:
-            self.model.argmax(T, self.d_next)
-            H.verify_greedy(self.d_next, self.d_ids, B, self.K, self.d_accept, self.d_recovery, self.d_packed)
+            self._greedy(lg, T, how)
+            H.verify_greedy(self.d_next, self.d_ids, B, K, self.d_accept, self.d_recovery, self.d_packed)
 
     def _launch(self, key, body) -> None:
         """Replay the captured hipGraph for `key`, capturing it on first use (after one eager warm-up run, which
@@ -463,6 +495,15 @@ class ModelRunner:
             return "captured"
         g.replay()
         return None
+
+    def _run_graph(self, key, stage, body) -> None:
+        """Stage the inputs and run `body` as the graph `key`.  The warm-up and capture runs of a first use consume what was staged
+        and advance device-side state (chained ids, step counters), so after a capture everything is staged again and the new graph
+        is replayed: what the caller reads was computed from exactly the staged inputs."""
+        stage()
+        if self._launch(key, body) == "captured":
+            stage()
+            self.graphs[(*key, self._ctx_hint)].replay()
 
     # ---------------------------------------------------------------------------------------------
     # public API
@@ -518,33 +559,15 @@ class ModelRunner:
             toks = self._read_tokens(B)
             return (toks, self.model.full_logits(B)) if draft_return_logits else toks
         if not last_only:
-            T = self._prepare_verify(seqs, ids_from_seq=True)
-            if self._launch(("verify_logits", B), lambda: self._body_verify(B, False)) == "captured":
-                self._prepare_verify(seqs, ids_from_seq=True)
-                self.graphs[("verify_logits", B, self._ctx_hint)].replay()
-            return self.model.full_logits(T)
-        self._prepare_decode(seqs)
-        temps = self._seq_temps(seqs)
-        pen = self._seq_penalties(seqs)
-        if pen:
-            self._upload_penalties(seqs)
-        if any(t > 0 for t in temps):       # autoregressive sampling (AutoRegressiveStep at temperature > 0)
-            self._ensure_stochastic()
-            self._upload(self.d_temps, temps, torch.float32)
-            filters = self._seq_filters(seqs)
-            if filters is not None:
-                self._upload_filters(filters)
-            key = (("decode_sf" if filters is not None else "decode_s") + ("_p" if pen else ""), B)
-            if self._launch(key, lambda: self._body_decode(B, False, sample=True, filt=filters is not None, pen=pen)) == "captured":
-                self._prepare_decode(seqs)
-                self.graphs[(*key, self._ctx_hint)].replay()
-        elif pen:                           # greedy with penalties: the full-logits argmax tail
-            if self._launch(("decode_p", B), lambda: self._body_decode(B, False, pen=True)) == "captured":
-                self._prepare_decode(seqs)
-                self.graphs[("decode_p", B, self._ctx_hint)].replay()
-        elif self._launch(("decode", B), lambda: self._body_decode(B, False)) == "captured":
+            self._run_graph(("verify_logits", B), lambda: self._prepare_verify(seqs, ids_from_seq=True), lambda: self._body_verify(B, False))
+            return self.model.full_logits(B * (self.K + 1))
+        how, values = self._seq_sampling(seqs)      # greedy, autoregressive sampling (AutoRegressiveStep at temperature > 0), penalised
+
+        def stage():
             self._prepare_decode(seqs)
-            self.graphs[("decode", B, self._ctx_hint)].replay()
+            self._stage_sampling(how, **values)
+
+        self._run_graph(("decode" + how.suffix, B), stage, lambda: self._body_decode(B, False, how=how))
         self._log_margins(B, [(s.seq_id, len(s)) for s in seqs])
         toks = self._read_tokens(B)
         return (toks, self.model.full_logits(B)) if draft_return_logits else toks
@@ -580,10 +603,31 @@ class ModelRunner:
         on = any(k > 0 for k in f[0]) or any(p < 1.0 for p in f[1]) or any(m > 0.0 for m in f[2])
         return f if on else None
 
-    def _upload_filters(self, filters) -> None:
-        self._upload(self.d_top_k, list(filters[0]), torch.int32)
-        self._upload(self.d_top_p, list(filters[1]), torch.float32)
-        self._upload(self.d_min_p, list(filters[2]), torch.float32)
+    def _seq_sampling(self, seqs, sample: bool | None = None, prefill: bool = False):
+        """(Sampling of the batch, the values _stage_sampling uploads for it).  sample: a verify samples whenever the round has a
+        temperature, the draft's included; prefill: a draft's prefill token is never used, so it is never penalised."""
+        temps = self._seq_temps(seqs)
+        if sample is None:
+            sample = any(t > 0 for t in temps)
+        filters = self._seq_filters(seqs) if sample else None
+        pen = self._seq_penalties(seqs) and not (prefill and self.is_draft)
+        return Sampling(sample, filters is not None, pen), dict(temps=temps, filters=filters, seqs=seqs)
+
+    def _stage_sampling(self, how: Sampling, temps=None, filters=None, seqs=None, back: int = 0, temps_q=None, ratio_rows=None) -> None:
+        """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, and the
+        penalty tables of `seqs` (back: see _upload_penalties).  A greedy batch without penalties uploads nothing."""
+        if how.sample:
+            self._ensure_stochastic()
+            self._upload(self.d_temps, list(temps), torch.float32)
+            if temps_q is not None:
+                self._upload(self.d_temps_q, [float(t) for t in temps_q], torch.float32)
+                self._upload(self.d_ratio, [int(r) for r in ratio_rows], torch.int32)
+        if how.filt:
+            self._upload(self.d_top_k, list(filters[0]), torch.int32)
+            self._upload(self.d_top_p, list(filters[1]), torch.float32)
+            self._upload(self.d_min_p, list(filters[2]), torch.float32)
+        if how.pen:
+            self._upload_penalties(seqs, back)
 
     def _filter(self, lg: torch.Tensor, rows: int, rows_per_param: int) -> None:
         """Truncate `rows` sampled rows in place, one parameter set (d_temps, d_top_k, d_top_p, d_min_p) per rows_per_param rows.
@@ -652,30 +696,14 @@ class ModelRunner:
                          self.d_pen_par[0], self.d_pen_par[1], self.d_pen_par[2], **extra)
 
     def _sample_or_argmax(self, seqs, B: int) -> None:
-        temps = self._seq_temps(seqs)
-        pen = not self.is_draft and self._seq_penalties(seqs)      # (a draft's prefill token is never used)
-        if pen:             # the prefill's first token: its history is the prompt
-            self._upload_penalties(seqs)
-            V = self.cfg.vocab_size
-            lg = self.model.full_logits(B)
-            self._penalize(lg, B, 1, None)
-            if not any(t > 0 for t in temps):
-                H.argmax_rows(lg, V, B, V, self.d_next)
-                return
-        if any(t > 0 for t in temps):
-            self._ensure_stochastic()
-            self._upload(self.d_temps, temps, torch.float32)
-            V = self.cfg.vocab_size
-            if not pen:
-                lg = self.model.full_logits(B)
-            filters = self._seq_filters(seqs)
-            if filters is not None:
-                self._upload_filters(filters)
-                self._filter(lg, B, 1)
-            H.sample_rows(lg, V, B, V, self.d_temps, 1, self.d_rng, 3, self.d_next)
-            H.rng_advance(self.d_rng)
+        """The prefill's first token, eagerly behind the (possibly replayed) forward; a penalised sequence's history is the prompt."""
+        how, values = self._seq_sampling(seqs, prefill=True)
+        self._stage_sampling(how, **values)
+        lg = self._rows(B, how)
+        if how.sample:
+            self._draw(lg, B, how, 1, 3)
         else:
-            self.model.argmax(B, self.d_next)
+            self._greedy(lg, B, how)
 
     def _read_tokens(self, n: int) -> list[int]:
         self.h_next[:n].copy_(self.d_next[:n], non_blocking=True)
@@ -692,34 +720,19 @@ class ModelRunner:
         only deposits x_K's KV, is deferred to `deposit_pending`: that KV is needed only if x_K gets accepted."""
         B, K = len(seqs), self.K
         self._check_chain_host()
-        temps = self._seq_temps(seqs)
-        sample = any(t > 0 for t in temps)
-        filters = self._seq_filters(seqs) if sample else None
-        filt = filters is not None
-        pen = self._seq_penalties(seqs)     # the draft is penalised like the target, or it proposes what the target will reject
-        key = ((("decode_chain_sf" if filt else "decode_chain_s") if sample else "decode_chain") + ("_p" if pen else ""), B)
-        if sample:
-            self._ensure_stochastic()
+        how, values = self._seq_sampling(seqs)      # the draft is penalised like the target, or it proposes what the target will reject
 
         def stage():
             self._prepare_decode(seqs)
             self.d_step.zero_()
             self.d_spec[:B, 0].copy_(self.d_ids[:B])
-            if sample:
-                self._upload(self.d_temps, temps, torch.float32)
-            if filt:
-                self._upload_filters(filters)
-            if pen:
-                self._upload_penalties(seqs)
+            self._stage_sampling(how, **values)
 
         def chain():                     # all K forwards in ONE hipGraph: no host gap between them
             for _ in range(K):
-                self._body_decode(B, True, sample=sample, filt=filt, pen=pen)
+                self._body_decode(B, True, how=how)
 
-        stage()
-        if self._launch(key, chain) == "captured":
-            stage()                      # the warm-up + capture runs disturbed the chained state
-            self.graphs[(*key, self._ctx_hint)].replay()
+        self._run_graph(("decode_chain" + how.suffix, B), stage, chain)
         self._post_chain_err()
         return self.d_spec[:B]
 
@@ -729,13 +742,15 @@ class ModelRunner:
         draft tokens were all accepted: feed x_K (now the second-to-last token; the new recovery token has been
         appended) at its position so that its KV exists before the next chain reads it.  No LM head, no sampling."""
         B = len(seqs)
-        self._stage_set = 1         # no host sync follows: the chain's staging must not reuse these pinned buffers
-        try:
-            self._prepare_decode(seqs, back=1)
-        finally:
-            self._stage_set = 0
-        if self._launch(("decode_deposit", B), lambda: self._body_decode(B, False, head=False)) == "captured":
-            self.graphs[("decode_deposit", B, self._ctx_hint)].replay()     # idempotent: same token, same slot
+
+        def stage():
+            self._stage_set = 1     # no host sync follows: the chain's staging must not reuse these pinned buffers
+            try:
+                self._prepare_decode(seqs, back=1)
+            finally:
+                self._stage_set = 0
+
+        self._run_graph(("decode_deposit", B), stage, lambda: self._body_decode(B, False, head=False))      # idempotent: same token, same slot
         self._post_chain_err()
 
     def logits_q(self, B: int) -> torch.Tensor:
@@ -749,38 +764,25 @@ class ModelRunner:
         Returns (new_suffixes, recovery_tokens)."""
         B, K = len(seqs), self.K
         self._acts_sliced = None
-        stochastic = temps_q is not None
-        filters = self._seq_filters(seqs) if stochastic else None
-        filt = filters is not None
-        pen = self._seq_penalties(seqs)
-        key = ((("verify_sf" if filt else "verify_s") if stochastic else "verify") + ("_p" if pen else ""), B)
-        if stochastic:
-            self._ensure_stochastic()
+        how, values = self._seq_sampling(seqs, sample=temps_q is not None)
+        if how.sample:
             if logits_q is None:        # greedy draft under a sampling target: q is one-hot, its logits are never read
                 if not hasattr(self, "_lq_dummy"):
                     self._lq_dummy = torch.zeros(self.seq_cap, K, self.cfg.vocab_size, dtype=torch.bfloat16, device=self.device)
                 logits_q = self._lq_dummy[:B]
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
-            if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):
-                self.graphs = {k: v for k, v in self.graphs.items() if not k[0].startswith("verify_s")}   # pointer is baked in the graph
+            if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):       # the pointer is baked in the sampling graphs
+                baked = {"verify" + Sampling(True, f, p).suffix for f in (False, True) for p in (False, True)}
+                self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in baked}
             self._lq_ptr = logits_q.data_ptr()
 
         def stage():
             self._prepare_verify(seqs, ids_from_seq=False)
             self.d_ids[:B * (K + 1)].copy_(speculations.reshape(-1))
-            if stochastic:
-                self._upload(self.d_temps, self._seq_temps(seqs), torch.float32)
-                self._upload(self.d_temps_q, [float(t) for t in temps_q], torch.float32)
-                self._upload(self.d_ratio, [int(r) for r in ratio_rows], torch.int32)
-            if filt:
-                self._upload_filters(filters)
-            if pen:             # token_ids ends in the K speculated positions: row j reads those from the inputs
-                self._upload_penalties(seqs, back=K)
+            # (penalties: token_ids ends in the K speculated positions, row j reads those from the inputs)
+            self._stage_sampling(how, **values, back=K, temps_q=temps_q, ratio_rows=ratio_rows)
 
-        stage()
-        if self._launch(key, lambda: self._body_verify(B, True, logits_q=logits_q, filt=filt, pen=pen)) == "captured":
-            stage()
-            self.graphs[(*key, self._ctx_hint)].replay()
+        self._run_graph(("verify" + how.suffix, B), stage, lambda: self._body_verify(B, True, logits_q=logits_q, how=how))
         self._log_margins(B * (K + 1), [(s.seq_id, s.num_tokens - (K + 1) + j + 1) for s in seqs for j in range(K + 1)])
         self.h_packed[:B].copy_(self.d_packed[:B], non_blocking=True)
         # the verify is in flight and the host is about to block on it: the moment for a co-located draft server to
@@ -862,12 +864,8 @@ class ModelRunner:
         (top_k [B], top_p [B], min_p [B]) truncates them first, as the target truncates its p."""
         B, K = len(rec), self.K
         self._check_chain_host()
-        sample = temps is not None and any(t > 0 for t in temps)
-        filt = sample and filters is not None
-        key = (("decode_chain_sf" if filt else "decode_chain_s") if sample else "decode_chain", B)
+        how = Sampling.explicit(temps, filters)
         self._note_ctx(max(num_tokens) + self._async_lookahead())
-        if sample:
-            self._ensure_stochastic()
 
         def stage():
             pos = [n - 1 for n in num_tokens]
@@ -877,19 +875,13 @@ class ModelRunner:
             self._upload(self.d_ctx, list(num_tokens), torch.int32)
             self._upload_tables(tables)
             self.d_step.zero_()
-            if sample:
-                self._upload(self.d_temps, list(temps), torch.float32)
-            if filt:
-                self._upload_filters(filters)
+            self._stage_sampling(how, temps, filters)
 
         def chain():
             for _ in range(K):
-                self._body_decode(B, True, sample=sample, filt=filt)
+                self._body_decode(B, True, how=how)
 
-        stage()
-        if self._launch(key, chain) == "captured":
-            stage()
-            self.graphs[(*key, self._ctx_hint)].replay()
+        self._run_graph(("decode_chain" + how.suffix, B), stage, chain)
         self._post_chain_err()
         return self.d_spec[:B, 1:].clone()
 
@@ -932,7 +924,6 @@ class ModelRunner:
         self._ensure_tree_buffers()
         self._check_chain_host()
         B, K = glue_ids.shape[0], self.K
-        key = ("glue_fork", B)
         self._note_ctx(max(num_tokens) + self._async_lookahead())
 
         def stage():
@@ -950,14 +941,11 @@ class ModelRunner:
             self._upload(self.d_fan, fl, torch.int32)
             self._upload(self.d_fan_off, [[sum(f[:j]) for j in range(len(f))] for f in fl], torch.int32)
 
-        stage()
-        if self._launch(key, lambda: self._body_glue_fork(B)) == "captured":
-            stage()
-            self.graphs[(*key, self._ctx_hint)].replay()
+        self._run_graph(("glue_fork", B), stage, lambda: self._body_glue_fork(B))
         self._post_chain_err()
         return self.d_forks[:B].clone()
 
-    def _body_tree(self, B: int, d: int, sample: bool = False, mq: int | None = None, filt: bool = False) -> None:
+    def _body_tree(self, B: int, d: int, how: Sampling = GREEDY, mq: int | None = None) -> None:
         mq = mq or self.mq          # tree width: MQ_LEN, or one member's slice of it under draft data-parallelism
         T = B * mq
         meta = AttnMeta(H.MODE_TREE, B, mq, self.d_tree_slots[d], self.d_tree_ctx[d], self.d_bt, q_per_seq=mq,
@@ -965,19 +953,8 @@ class ModelRunner:
                         ctx_hint=self._ctx_hint)
         self.model.forward(self.d_ids, self.d_tree_pos[d], T, meta)
         self.model.compute_logits(T)
-        if sample:          # one temperature per sequence = per MQ_LEN branch rows; keep every branch's logits for logits_q
-            V = self.cfg.vocab_size
-            lg = self.model.full_logits(T)
-            if filt:        # one parameter set per sequence = per mq branch rows
-                self._filter(lg, T, mq)
-            H.store_step_rows(lg, V, self.d_tree_logits, T, V, self.K, self.d_steps_const[d:])
-            if self.sx is not None:          # Sampler(is_tree=True) with sampler_x (sampler.py:29-31)
-                H.topk_rows(lg, V, T, V, self.sx_k, self.d_boost)
-                H.sample_rows(lg, V, T, V, self.d_temps, mq, self.d_rng, 4, self.d_next, boost_idx=self.d_boost,
-                              boost_k=self.sx_k, boost_x=self.sx)
-            else:
-                H.sample_rows(lg, V, T, V, self.d_temps, mq, self.d_rng, 4, self.d_next)
-            H.rng_advance(self.d_rng)
+        if how.sample:      # one parameter set per sequence = per mq branch rows; keep every branch's logits for logits_q
+            self._draw(self._rows(T, how), T, how, mq, 4, keep=(self.d_tree_logits, self.d_steps_const[d:]), boost=True)
         elif self.model.has_argmax_parts(T):
             # one launch writes the tokens, the next step's input ids and column d of the [T][K] token table
             self.model.argmax(T, self.d_next, self.d_ids, self.d_tree_tokens.view(-1)[d:], self.K)
@@ -997,11 +974,8 @@ class ModelRunner:
         assert mq <= self.mq
         T = B * mq
         self._note_ctx(max(num_tokens) + self._async_lookahead())
-        sample = temps is not None and any(t > 0 for t in temps)
-        filt = sample and filters is not None
-        if sample:
-            self._ensure_stochastic()
-            if self.d_tree_logits is None:
+        how = Sampling.explicit(temps, filters)
+        if how.sample and self.d_tree_logits is None:
                 self.d_tree_logits = torch.zeros(self.max_bs * self.mq, K, self.cfg.vocab_size, dtype=torch.bfloat16, device=self.device)
 
         def stage():
@@ -1023,20 +997,13 @@ class ModelRunner:
             self._upload(self.d_jidx_flat, [v for j in jlists for v in j], torch.int32)     # packed [B][mq]
             self._upload_tables(tables)
             self.d_ids[:T].copy_(forks.reshape(-1))
-            if sample:
-                self._upload(self.d_temps, list(temps), torch.float32)
-            if filt:
-                self._upload_filters(filters)
+            self._stage_sampling(how, temps, filters)
 
         def all_steps():                 # the K tree steps in ONE hipGraph (each step has its own static metadata rows)
             for d in range(K):
-                self._body_tree(B, d, sample, mq, filt)
+                self._body_tree(B, d, how, mq)
 
-        stage()
-        key = (("tree_sf" if filt else "tree_s") if sample else "tree", B, mq)
-        if self._launch(key, all_steps) == "captured":
-            self.d_ids[:T].copy_(forks.reshape(-1))      # the eager warm-up consumed the inputs
-            self.graphs[(*key, self._ctx_hint)].replay()
+        self._run_graph(("tree" + how.suffix, B, mq), stage, all_steps)
         self._post_chain_err()
         return self.d_tree_tokens[:T].clone()
 
