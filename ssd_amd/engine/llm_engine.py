@@ -1,7 +1,8 @@
 """LLMEngine: request loop, metrics, step wiring (reference ssd/engine/llm_engine.py:39-381).
 
 Public behaviour kept: ``LLM(model, **Config fields)``; ``generate(prompts, sampling_params, use_tqdm=True,
-stream_callback=None) -> (outputs, METRICS)`` with ``outputs[i] = {"text", "token_ids"}``; the METRICS keys.
+stream_callback=None) -> (outputs, METRICS)`` with ``outputs[i] = {"text", "token_ids"}``; the METRICS keys.  A request with
+``SamplingParams(logprobs=N)`` also gets ``"logprobs"`` (one record per token) and ``"cumulative_logprob"``.
 
 Process model (differs by design): one process per GPU, SPMD.  Under ``torchrun`` every rank constructs the same
 engine and calls ``generate`` with the same requests; tensor-parallel ranks stay in lock step through the RCCL
@@ -96,6 +97,7 @@ class LLMEngine:
 
         self.draft_runner = None
         self._capped_ids: set[int] = set()
+        self._logprobs_out: dict[int, list] = {}        # seq id -> the records of a finished request that asked (step() fills it)
         self.async_link = None
         self.draft_server = None
         if self.topo.role == "draft":               # dedicated draft GPU of async speculation
@@ -196,6 +198,15 @@ class LLMEngine:
                 if cap is not None and sampling_params.logit_bias and len(sampling_params.logit_bias) > cap:
                     raise ValueError(f"logit_bias has {len(sampling_params.logit_bias)} entries: the history table of "
                                      f"{type(runner).__name__} holds at most {cap} biased ids beside the sequence's own tokens")
+        if sampling_params is not None and sampling_params.logprobs is not None:
+            # log-probabilities come from the target's raw rows (csrc/logprob.hip): the draft is never asked, so an asynchronous draft
+            # on its own GPU is fine; a tensor-parallel target holds a shard of the vocabulary per rank and refuses
+            runner = getattr(self, "model_runner", None)
+            if runner is not None and not getattr(runner, "supports_logprobs", False):
+                raise ValueError(f"logprobs is not supported by {type(runner).__name__}: this runner has no log-probability kernel")
+            if getattr(runner, "tp_size", 1) > 1:
+                raise ValueError(f"logprobs is not supported with a tensor-parallel target (tp_size = {runner.tp_size}): every rank "
+                                 f"holds a shard of the vocabulary")
         self.scheduler.add(Sequence(prompt, sampling_params))
 
     def step(self, step: InferenceStep):
@@ -204,8 +215,12 @@ class LLMEngine:
         capped = []
         for s in self.scheduler.pop_capped():          # stopped at max_model_len (Scheduler._length_capped)
             toks = s.completion_token_ids
+            if s.logprobs is not None:
+                self._logprobs_out[s.seq_id] = s.completion_logprobs
             if s.first_token_streamed is not None:      # streamed at the prefill, capped before the round that appends it:
                 toks = toks + [s.first_token_streamed]  # the result must carry what the stream already delivered
+                if s.logprobs is not None:              # ... and that token's record
+                    self._logprobs_out[s.seq_id] = s.completion_logprobs + [s.recovery_logprob]
             capped.append((s.seq_id, toks))
             self._capped_ids.add(s.seq_id)
         if not seqs:            # every runnable sequence was one of those
@@ -218,6 +233,9 @@ class LLMEngine:
         else:
             METRICS["decode_total_time"] += dt
             METRICS["decode_total_tokens"] += n
+        for s in seqs:
+            if s.is_finished and s.logprobs is not None:
+                self._logprobs_out[s.seq_id] = s.completion_logprobs
         return capped + [(s.seq_id, s.completion_token_ids) for s in seqs if s.is_finished]
 
     def is_finished(self) -> bool:
@@ -307,6 +325,7 @@ class LLMEngine:
         for k, v in _fresh_metrics().items():
             METRICS[k] = v
         self._capped_ids.clear()            # finish reasons are per generate() call
+        self._logprobs_out.clear()
         if not isinstance(sampling_params, list):
             sampling_params = [sampling_params] * len(prompts)
         for prompt, sp in zip(prompts, sampling_params):
@@ -361,6 +380,11 @@ class LLMEngine:
             # max_new_tokens / EOS because its next speculation step would not fit the model length
             result.append({"text": text, "token_ids": toks,
                            "finish_reason": "max_model_len" if seq_id in self._capped_ids else "stop"})
+            if seq_id in self._logprobs_out:        # SamplingParams(logprobs=N): one record per token, raw log-probabilities
+                records = self._logprobs_out[seq_id]
+                assert len(records) == len(toks), (len(records), len(toks))
+                result[-1]["logprobs"] = records
+                result[-1]["cumulative_logprob"] = float(sum(r["logprob"] for r in records))
         if not stream_callback and self.config.verbose:
             self.log_metrics()
         # a snapshot, not the module-level dict itself (the reference returns the global: two engines run one after the other in

@@ -23,6 +23,7 @@ import torch.distributed as dist
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import filter_ops as HF
 from ssd_amd.hip import penalty_ops as HP
+from ssd_amd.hip import logprob_ops as HL
 from ssd_amd.hip.lib import load_library
 from ssd_amd.model import HipDecoder, AttnMeta
 from ssd_amd.model_config import ModelConfig
@@ -36,11 +37,12 @@ class Sampling(NamedTuple):
     sample: bool = False    # some temperature > 0: draw with the Gumbel-max sampler (a verify: ratio acceptance)
     filt: bool = False      # some sampled sequence has top_k / top_p / min_p: truncate the rows first
     pen: bool = False       # some sequence has a penalty or a logit bias: adjust the raw rows in front of everything else
+    lp: bool = False        # some sequence asked for log-probabilities (the target only): read the raw rows first, pick after the token
 
     @property
     def suffix(self) -> str:
         """What a graph's name carries behind "decode" / "decode_chain" / "verify" / "tree"."""
-        return ("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "")
+        return ("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "") + ("_l" if self.lp else "")
 
     @classmethod
     def explicit(cls, temps, filters) -> "Sampling":
@@ -57,6 +59,7 @@ class ModelRunner:
     PREFILL_GRAPH_MAX_T = 1024      # longer prefills are GPU-bound by far: launch overhead does not matter
     supports_logit_filters = True   # top_k / top_p / min_p (csrc/filter.hip); LLMEngine.add_request refuses them on runners without it
     supports_logit_penalties = True # repetition / presence / frequency penalty, logit_bias (csrc/penalty.hip); refused likewise
+    supports_logprobs = True        # SamplingParams(logprobs=N): raw log-probabilities of the target's rows (csrc/logprob.hip); likewise
     PENALTY_MAX_BIAS = 1024         # logit_bias entries one request may carry: the history table holds max_model_len + this many ids
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
@@ -163,6 +166,9 @@ class ModelRunner:
         self.margin_log = None      # tests: set to {} to record (seq_id, position) -> top-2 margin of every greedy decision (TP = 1)
         self.graph_pool = None
         self.stream = torch.cuda.Stream(device)
+        # records of the tokens the last run / verify_chain returned, for the sequences that asked (else None): run -> one record or
+        # None per sequence; verify_chain -> per sequence the records of its accepted draft tokens and of the new recovery token
+        self.last_logprobs = None
 
     def _setup_custom_ar(self, want: bool | None) -> None:
         """Enable the one-shot all-reduce for the small TP sums when (a) tensor parallelism is on, (b) it is not
@@ -432,6 +438,9 @@ class ModelRunner:
         if not head:        # KV deposit only (the (K+1)-th draft forward, speculator_sync.py:55-56): no LM head / sampling
             return
         self.model.compute_logits(B)
+        if how.lp:          # (the target's decode only: a draft never builds how.lp)
+            assert not chain
+            self._logprob_rows(B, how, 1)
         lg = self._rows(B, how, 1, "chain" if chain else None)      # a chain step also sees the chain's own tokens so far
         if how.sample:
             self._draw(lg, B, how, 1, 1, keep=(self.d_logits_q, self.d_step) if chain else None, boost=chain and self.is_draft)
@@ -442,6 +451,8 @@ class ModelRunner:
             return
         else:
             self._greedy(lg, B, how)
+        if how.lp:
+            self._logprob_pick(B, how)
         if chain:
             H.draft_advance(self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                             self.block_size, self.d_spec, self.K, self.d_step, B)
@@ -451,6 +462,8 @@ class ModelRunner:
         T = B * (K + 1)
         self.model.forward(self.d_ids, self.d_pos, T, self._meta("verify", B))
         self.model.compute_logits(T)
+        if how.lp:
+            self._logprob_rows(T, how, K + 1)
         # penalised: row j with the history autoregressive decoding would have had there, the table + inputs 1..j of the round
         lg = self._rows(T, how, K + 1, "prefix")
         if how.sample:      # temperature > 0: ratio acceptance + residual resampling (utils/verify.py:50-167)
@@ -473,6 +486,9 @@ class ModelRunner:
         elif greedy_tail:
             self._greedy(lg, T, how)
             H.verify_greedy(self.d_next, self.d_ids, B, K, self.d_accept, self.d_recovery, self.d_packed)
+        if how.lp:          # accepted inputs and the recovery token of every sequence, from the raw rows
+            HL.logprob_pick_verify(self._logprob_src(how), V, B, K, V, self.d_ids, self.d_accept, self.d_recovery, self.d_lp_lse,
+                                   self.d_lp_ntop, self.d_lp_out)
 
     def _launch(self, key, body) -> None:
         """Replay the captured hipGraph for `key`, capturing it on first use (after one eager warm-up run, which
@@ -519,15 +535,18 @@ class ModelRunner:
         B = len(seqs)
         if is_prefill and B > self.seq_cap:
             assert not draft_return_logits
-            toks, acts = [], []
+            toks, acts, lps = [], [], []
             for i in range(0, B, self.seq_cap):
                 part = seqs[i:i + self.seq_cap]
                 toks.extend(self.run(part, True, last_only))
+                lps.extend(self.last_logprobs or [None] * len(part))
                 if self.model.acts is not None:         # EAGLE-3 taps: the static buffer only holds the last slice
                     acts.append(self.model.acts[:sum(len(s) - s.num_cached_tokens for s in part)].clone())
             self._acts_sliced = torch.cat(acts, dim=0) if acts else None
+            self.last_logprobs = lps if any(r is not None for r in lps) else None
             return toks
         self._acts_sliced = None
+        self.last_logprobs = None
         if is_prefill:
             T, max_q = self._prepare_prefill(seqs)
 
@@ -555,8 +574,10 @@ class ModelRunner:
                         del self.graphs[k]
                 self._launch(key, body)             # "captured": the eager warm-up run already produced this call's result
             self._log_margins(B, [(s.seq_id, len(s)) for s in seqs])
-            self._sample_or_argmax(seqs, B)
-            toks = self._read_tokens(B)
+            how = self._sample_or_argmax(seqs, B)
+            toks = self._read_tokens(B, lp=how.lp)
+            if how.lp:
+                self.last_logprobs = self._records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
             return (toks, self.model.full_logits(B)) if draft_return_logits else toks
         if not last_only:
             self._run_graph(("verify_logits", B), lambda: self._prepare_verify(seqs, ids_from_seq=True), lambda: self._body_verify(B, False))
@@ -569,7 +590,9 @@ class ModelRunner:
 
         self._run_graph(("decode" + how.suffix, B), stage, lambda: self._body_decode(B, False, how=how))
         self._log_margins(B, [(s.seq_id, len(s)) for s in seqs])
-        toks = self._read_tokens(B)
+        toks = self._read_tokens(B, lp=how.lp)
+        if how.lp:
+            self.last_logprobs = self._records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
         return (toks, self.model.full_logits(B)) if draft_return_logits else toks
 
     def eagle_acts(self, n: int) -> torch.Tensor:
@@ -611,7 +634,8 @@ class ModelRunner:
             sample = any(t > 0 for t in temps)
         filters = self._seq_filters(seqs) if sample else None
         pen = self._seq_penalties(seqs) and not (prefill and self.is_draft)
-        return Sampling(sample, filters is not None, pen), dict(temps=temps, filters=filters, seqs=seqs)
+        lp = not self.is_draft and any(getattr(s, "logprobs", None) is not None for s in seqs)     # the target's distribution only
+        return Sampling(sample, filters is not None, pen, lp), dict(temps=temps, filters=filters, seqs=seqs)
 
     def _stage_sampling(self, how: Sampling, temps=None, filters=None, seqs=None, back: int = 0, temps_q=None, ratio_rows=None) -> None:
         """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, and the
@@ -628,6 +652,69 @@ class ModelRunner:
             self._upload(self.d_min_p, list(filters[2]), torch.float32)
         if how.pen:
             self._upload_penalties(seqs, back)
+        if how.lp:          # the N of every sequence; -1 = did not ask: the kernels skip its rows
+            self._ensure_logprob(how.pen)
+            self._upload(self.d_lp_ntop, [-1 if getattr(s, "logprobs", None) is None else int(s.logprobs) for s in seqs], torch.int32)
+
+    def _ensure_logprob(self, copy: bool) -> None:
+        """Device buffers of csrc/logprob.hip, sized by the model's logit rows, with the pinned mirrors of what the host reads
+        (allocated on first use).  copy: also the raw-row copy a penalised batch picks from (rows x V bf16, on ITS first use)."""
+        R, V = self.model.max_logit_rows, self.cfg.vocab_size
+        dev = dict(device=self.device)
+        if not hasattr(self, "d_lp_ntop"):
+            assert self.tp_size == 1, "log-probabilities need the whole vocabulary on one rank"
+            self.d_lp_ntop = torch.full((self.seq_cap,), -1, dtype=torch.int32, **dev)
+            self.d_lp_lse = torch.zeros(R, dtype=torch.float32, **dev)
+            self.d_lp_out = torch.zeros(R, dtype=torch.float32, **dev)
+            self.d_lp_top_val = torch.zeros(R, HL.MAX_N, dtype=torch.float32, **dev)
+            self.d_lp_top_id = torch.zeros(R, HL.MAX_N, dtype=torch.int32, **dev)
+            self.d_lp_ws = torch.zeros(HL.logprob_rows_ws_bytes(R, V) // 4, dtype=torch.float32, **dev)
+            self.d_lp_raw = None
+            self.h_lp_out = torch.zeros(R, dtype=torch.float32).pin_memory()
+            self.h_lp_top_val = torch.zeros(R, HL.MAX_N, dtype=torch.float32).pin_memory()
+            self.h_lp_top_id = torch.zeros(R, HL.MAX_N, dtype=torch.int32).pin_memory()
+        if copy and self.d_lp_raw is None:
+            self.d_lp_raw = torch.zeros(R, V, dtype=torch.bfloat16, **dev)
+
+    def _logprob_rows(self, rows: int, how: Sampling, rows_per_param: int) -> None:
+        """Behind compute_logits and in front of _rows: log-sum-exp and top entries of the RAW rows.  A penalised batch also keeps a
+        copy of them (penalties rewrite entries a chosen token may sit on; truncation only writes -inf over entries that can no
+        longer be chosen, so the live rows serve there)."""
+        V = self.cfg.vocab_size
+        HL.logprob_rows(self.model.logits, V, rows, V, self.d_lp_ntop, rows_per_param, self.d_lp_lse, self.d_lp_top_val, self.d_lp_top_id,
+                        self.d_lp_ws, raw_copy=self.d_lp_raw if how.pen else None, raw_ld=V if how.pen else 0)
+
+    def _logprob_src(self, how: Sampling) -> torch.Tensor:
+        return self.d_lp_raw if how.pen else self.model.logits
+
+    def _logprob_pick(self, rows: int, how: Sampling) -> None:
+        """d_lp_out = raw log-probability of d_next, row by row (decode and prefill rows: one sequence each)."""
+        V = self.cfg.vocab_size
+        HL.logprob_pick(self._logprob_src(how), V, rows, V, self.d_next, self.d_lp_lse, self.d_lp_ntop, 1, self.d_lp_out)
+
+    def _post_logprobs(self, rows: int) -> None:
+        """Queue the D2H copies of what the host reads, in front of the synchronise the step performs anyway (lse stays on the device)."""
+        self.h_lp_out[:rows].copy_(self.d_lp_out[:rows], non_blocking=True)
+        self.h_lp_top_val[:rows].copy_(self.d_lp_top_val[:rows], non_blocking=True)
+        self.h_lp_top_id[:rows].copy_(self.d_lp_top_id[:rows], non_blocking=True)
+
+    def _records(self, seqs, row_tokens, single: bool = False):
+        """The records of `seqs` from the pinned mirrors (after the synchronise).  row_tokens: per sequence the (row, token) pairs of
+        its tokens, in order; sequences that did not ask get None.  single: one record per sequence instead of a list."""
+        n = 1 + max(r for pairs in row_tokens for r, _ in pairs)
+        lp, tv, ti = self.h_lp_out[:n].tolist(), self.h_lp_top_val[:n].tolist(), self.h_lp_top_id[:n].tolist()
+        out = []
+        for s, pairs in zip(seqs, row_tokens):
+            N = getattr(s, "logprobs", None)
+            if N is None:
+                out.append(None)
+                continue
+            recs = []
+            for r, tok in pairs:
+                k = sum(1 for i in ti[r][:N] if i >= 0)         # min(N, V): slots past the row's entries hold -1 / -inf
+                recs.append({"token_id": int(tok), "logprob": lp[r], "top_ids": ti[r][:k], "top_logprobs": tv[r][:k]})
+            out.append(recs[0] if single else recs)
+        return out
 
     def _filter(self, lg: torch.Tensor, rows: int, rows_per_param: int) -> None:
         """Truncate `rows` sampled rows in place, one parameter set (d_temps, d_top_k, d_top_p, d_min_p) per rows_per_param rows.
@@ -695,18 +782,25 @@ class ModelRunner:
         HP.penalize_rows(lg, V, rows, V, rows_per_seq, self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.pen_tab_ld, self.d_pen_len,
                          self.d_pen_par[0], self.d_pen_par[1], self.d_pen_par[2], **extra)
 
-    def _sample_or_argmax(self, seqs, B: int) -> None:
+    def _sample_or_argmax(self, seqs, B: int) -> Sampling:
         """The prefill's first token, eagerly behind the (possibly replayed) forward; a penalised sequence's history is the prompt."""
         how, values = self._seq_sampling(seqs, prefill=True)
         self._stage_sampling(how, **values)
+        if how.lp:
+            self._logprob_rows(B, how, 1)
         lg = self._rows(B, how)
         if how.sample:
             self._draw(lg, B, how, 1, 3)
         else:
             self._greedy(lg, B, how)
+        if how.lp:
+            self._logprob_pick(B, how)
+        return how
 
-    def _read_tokens(self, n: int) -> list[int]:
+    def _read_tokens(self, n: int, lp: bool = False) -> list[int]:
         self.h_next[:n].copy_(self.d_next[:n], non_blocking=True)
+        if lp:
+            self._post_logprobs(n)
         torch.cuda.current_stream().synchronize()
         self._check_collectives()
         return self.h_next[:n].tolist()
@@ -764,6 +858,7 @@ class ModelRunner:
         Returns (new_suffixes, recovery_tokens)."""
         B, K = len(seqs), self.K
         self._acts_sliced = None
+        self.last_logprobs = None
         how, values = self._seq_sampling(seqs, sample=temps_q is not None)
         if how.sample:
             if logits_q is None:        # greedy draft under a sampling target: q is one-hot, its logits are never read
@@ -772,7 +867,8 @@ class ModelRunner:
                 logits_q = self._lq_dummy[:B]
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
             if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):       # the pointer is baked in the sampling graphs
-                baked = {"verify" + Sampling(True, f, p).suffix for f in (False, True) for p in (False, True)}
+                on_off = (False, True)
+                baked = {"verify" + Sampling(True, f, p, l).suffix for f in on_off for p in on_off for l in on_off}
                 self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in baked}
             self._lq_ptr = logits_q.data_ptr()
 
@@ -785,6 +881,8 @@ class ModelRunner:
         self._run_graph(("verify" + how.suffix, B), stage, lambda: self._body_verify(B, True, logits_q=logits_q, how=how))
         self._log_margins(B * (K + 1), [(s.seq_id, s.num_tokens - (K + 1) + j + 1) for s in seqs for j in range(K + 1)])
         self.h_packed[:B].copy_(self.d_packed[:B], non_blocking=True)
+        if how.lp:
+            self._post_logprobs(B * (K + 1))
         # the verify is in flight and the host is about to block on it: the moment for a co-located draft server to
         # enqueue its next round on its own stream (engine/draft_runner.py run_deferred)
         hook = getattr(self, "overlap_hook", None)
@@ -795,6 +893,9 @@ class ModelRunner:
         rows = self.h_packed[:B].tolist()
         suffixes = [r[2:3 + r[0]] for r in rows]
         recovery = [r[1] for r in rows]
+        if how.lp:          # row (b, j) predicted input j + 1 (accepted while j < a) or, at j = a, the recovery token
+            self.last_logprobs = self._records(seqs, [[(b * (K + 1) + j, r[3 + j] if j < r[0] else r[1]) for j in range(r[0] + 1)]
+                                                      for b, r in enumerate(rows)])
         return suffixes, recovery
 
     # ---------------------------------------------------------------------------------------------

@@ -139,6 +139,8 @@ class Scheduler:
     def preempt(self, seq: Sequence) -> None:
         seq.status = SequenceStatus.WAITING
         seq.recovery_token_id = None
+        if seq.first_token_streamed is None:        # (a pinned first token is kept by the re-prefill, and so is its record)
+            seq.recovery_logprob = None
         self.block_manager.deallocate(seq)
         if self.speculate:
             self.draft_block_manager.deallocate(seq)
@@ -148,10 +150,13 @@ class Scheduler:
         seq.extend_count, seq.extend_eagle_acts, seq.extend_token_ids = 0, None, None     # scheduler.py:143-146
 
     # ---- autoregressive post-step (reference scheduler.py:149-170) ----
-    def postprocess(self, seqs: list[Sequence], token_ids: list[int], is_prefill: bool) -> None:
+    def postprocess(self, seqs: list[Sequence], token_ids: list[int], is_prefill: bool, logprobs=None) -> None:
+        """logprobs: per sequence the record of its token, or None (sequences that did not ask)."""
         bm = self.block_manager
-        for seq, tok in zip(seqs, token_ids):
+        for i, (seq, tok) in enumerate(zip(seqs, token_ids)):
             seq.append_token(tok)
+            if seq.logprobs is not None:
+                seq.logprob_records.append(logprobs[i])
             if is_prefill:
                 seq.num_cached_tokens = seq.num_prompt_tokens
             else:
@@ -188,9 +193,14 @@ class Scheduler:
                     bm.unref(block_id)
                 setattr(seq, table_name, table[:-extra])
 
-    def _commit_suffix(self, seq: Sequence, suffix: list[int], recovery: int) -> None:
+    def _commit_suffix(self, seq: Sequence, suffix: list[int], recovery: int, records=None) -> None:
+        """records: of the round's a accepted draft tokens and of the new recovery token.  The suffix is [previous recovery token]
+        + accepted tokens, possibly clipped: its records are the pending recovery record + the accepted ones, clipped with it."""
         n = len(suffix)
         assert n >= 1
+        if seq.logprobs is not None:
+            seq.logprob_records.extend(([seq.recovery_logprob] + list(records[:-1]))[:n])
+            seq.recovery_logprob = records[-1]
         seq.token_ids.extend(suffix)
         seq.num_tokens += n
         seq.last_token = suffix[-1]
@@ -211,11 +221,11 @@ class Scheduler:
                     self.draft_block_manager.finalize_block(seq, seq.draft_block_table, idx)
 
     def postprocess_speculate(self, seqs: list[Sequence], new_suffixes: list[list[int]], next_recovery_tokens: list[int],
-                              eagle_acts=None) -> None:
+                              eagle_acts=None, logprobs=None) -> None:
         for i, (seq, suffix, rec) in enumerate(zip(seqs, new_suffixes, next_recovery_tokens)):
             suffix, finished = self._clip_suffix(seq, suffix)
             self._return_excess_blocks(seq, len(suffix))
-            self._commit_suffix(seq, suffix, rec)
+            self._commit_suffix(seq, suffix, rec, logprobs[i] if seq.logprobs is not None else None)
             if eagle_acts is not None:          # scheduler.py:303-320; eagle_acts [B, K+1, taps * h_target]
                 n = len(suffix)                 # suffix = [recovery, accepted draft tokens...]
                 seq.last_target_hidden_state = eagle_acts[i, min(n - 1, eagle_acts.shape[1] - 1)]

@@ -54,6 +54,13 @@ class Sequence:
             self._pen = {t: [0, False, v] for t, v in (self.logit_bias or {}).items()}
         self.max_new_tokens = sp.max_new_tokens
         self.ignore_eos = sp.ignore_eos
+        # log-probabilities (include/ssd_hip_logprob.h): the N asked for (None = off) and one record {"token_id", "logprob", "top_ids",
+        # "top_logprobs"} per generated token -- record i belongs to token_ids[num_request_prompt_tokens + i]: like the penalties'
+        # history it is keyed from the request's own prompt, because a preemption moves num_prompt_tokens.  recovery_logprob is the
+        # record of recovery_token_id; it joins the list in the round that commits that token
+        self.logprobs = sp.logprobs
+        self.logprob_records: list[dict] = []
+        self.recovery_logprob: dict | None = None
         # EAGLE-3 (reference sequence.py:23-24,47-51): the target activation that conditions the next recovery token, and
         # the accepted draft tokens + their target activations that the draft re-deposits ("extends") at the next glue
         self.last_target_hidden_state = None
@@ -127,6 +134,11 @@ class Sequence:
     @property
     def completion_token_ids(self) -> list[int]:
         return self.token_ids[self.num_prompt_tokens:]
+
+    @property
+    def completion_logprobs(self) -> list[dict]:
+        """The records of completion_token_ids (after a preemption: of the tokens generated since, as completion_token_ids)."""
+        return self.logprob_records[self.num_prompt_tokens - self.num_request_prompt_tokens:]
 
     @property
     def num_blocks(self) -> int:

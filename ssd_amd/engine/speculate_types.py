@@ -20,6 +20,7 @@ class VerifyResult:
     new_suffixes: list           # per sequence: [recovery] + accepted draft tokens
     recovery_tokens: list        # per sequence: the next recovery token
     eagle_acts: Any = None
+    logprobs: Any = None         # per sequence: the records of the accepted draft tokens and of the next recovery token, or None
 
 
 class SpeculatorBase(ABC):

@@ -26,7 +26,10 @@ class AutoRegressiveStep(InferenceStep):
 
     def _step(self, seqs, is_prefill: bool) -> int:
         token_ids = self.model_runner.call("run", seqs, is_prefill)
-        self.scheduler.postprocess(seqs, token_ids, is_prefill)
+        if any(s.logprobs is not None for s in seqs):       # the records of those tokens, left beside them by the runner
+            self.scheduler.postprocess(seqs, token_ids, is_prefill, logprobs=self.model_runner.last_logprobs)
+        else:
+            self.scheduler.postprocess(seqs, token_ids, is_prefill)
         return sum(len(s) for s in seqs) if is_prefill else len(seqs)
 
     def prefill(self, seqs) -> int:
@@ -72,8 +75,9 @@ class SpecDecodeStep(InferenceStep):
         t2 = prof.sync_now() if trace else 0.0
         for seq, snap in zip(seqs, saved):      # undo the lookahead applied by speculate + verify
             seq.restore(snap)
+        lp = {"logprobs": out.logprobs} if out.logprobs is not None else {}
         self.scheduler.postprocess_speculate(seqs, out.new_suffixes, out.recovery_tokens,
-                                             eagle_acts=out.eagle_acts if self.eagle else None)
+                                             eagle_acts=out.eagle_acts if self.eagle else None, **lp)
         toks = sum(len(s) for s in out.new_suffixes)
         if trace:
             t3 = prof.sync_now()

@@ -25,13 +25,17 @@ class Verifier(VerifierBase):
             for s in seqs:
                 assert s.num_cached_tokens == 0, "EAGLE-3 needs the activations of the whole prompt (no prefix-cache hits)"
             acts = self.target_model_runner.eagle_acts(sum(len(s) for s in seqs)).clone()
+        asked = any(s.logprobs is not None for s in seqs)
+        records = self.target_model_runner.last_logprobs if asked else None
         off = 0
-        for seq, tok in zip(seqs, token_ids):
+        for i, (seq, tok) in enumerate(zip(seqs, token_ids)):
             # already handed to the stream (LLMEngine.generate) and not yet appended: a re-prefill (preemption before the
             # first round) must not flip it.  The pin is cleared by Sequence.append_token, so a sequence preempted AFTER its
             # first round -- whose completion count restarts at 0 -- takes the freshly computed token
             pinned = seq.first_token_streamed
             seq.recovery_token_id = tok if pinned is None else pinned
+            if seq.logprobs is not None and (pinned is None or seq.recovery_logprob is None):
+                seq.recovery_logprob = records[i]      # (the pinned token keeps the record it was streamed with)
             if eagle:
                 off += len(seq)
                 seq.last_target_hidden_state = acts[off - 1]
@@ -69,4 +73,5 @@ class Verifier(VerifierBase):
         if eagle:       # verifier.py:145-147
             B = len(seqs)
             acts = self.target_model_runner.eagle_acts(B * (self.lookahead + 1)).clone().view(B, self.lookahead + 1, -1)
-        return VerifyResult(new_suffixes, recovery, acts)
+        records = self.target_model_runner.last_logprobs if any(s.logprobs is not None for s in seqs) else None
+        return VerifyResult(new_suffixes, recovery, acts, records)

@@ -1,8 +1,15 @@
 """SamplingParams -- the reference's fields and defaults (ssd/sampling_params.py:4-9) plus the truncation every other LLM.generate offers:
 top_k / top_p / min_p, applied in the Hugging Face order after the temperature (include/ssd_hip_filter.h has the exact semantics), and,
-before the temperature, repetition / presence / frequency penalties and logit bias (include/ssd_hip_penalty.h)."""
+before the temperature, repetition / presence / frequency penalties and logit bias (include/ssd_hip_penalty.h).
+
+``logprobs=N`` asks for the log-probability of every generated token (N = 0) and, beside it, for the N most probable tokens of that
+position (N = 1..20).  They are RAW log-probabilities: log_softmax of the target's bf16 logits, taken before penalties, logit bias,
+temperature and truncation (include/ssd_hip_logprob.h) -- whatever the decoding mode, the target's distribution."""
 import math
 from dataclasses import dataclass
+
+
+MAX_LOGPROBS = 20       # SSD_LOGPROB_MAX_N
 
 
 def _is_real(v) -> bool:
@@ -22,6 +29,7 @@ class SamplingParams:
     presence_penalty: float = 0.0       # subtracted once from the logit of every token already in the output; 0.0 = off
     frequency_penalty: float = 0.0      # subtracted per occurrence in the output; 0.0 = off
     logit_bias: dict | None = None      # token id -> value in [-100, 100] added to that token's logit; None = off
+    logprobs: int | None = None         # None = off; 0 = each generated token's raw log-probability; 1..20 = also the N most probable
 
     def __post_init__(self):
         if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or self.top_k < 0:
@@ -44,6 +52,10 @@ class SamplingParams:
                     raise ValueError(f"logit_bias keys must be integers >= 0, got {t!r}")
                 if not _is_real(v) or not -100.0 <= v <= 100.0:
                     raise ValueError(f"logit_bias values must be finite and within [-100, 100], got {v!r} for token {t}")
+
+        if self.logprobs is not None and (isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int)
+                                          or not 0 <= self.logprobs <= MAX_LOGPROBS):
+            raise ValueError(f"logprobs must be None (off) or an integer in [0, {MAX_LOGPROBS}], got {self.logprobs!r}")
 
     @property
     def active_penalties(self) -> list[str]:
