@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ssd_amd.config import Config  # noqa: E402
 from ssd_amd.engine.llm_engine import hip_runner_factory  # noqa: E402
 from ssd_amd.hip import ops as H  # noqa: E402
-from ssd_amd.model import AttnMeta  # noqa: E402
+from ssd_amd.model import AttnMeta, NORMED  # noqa: E402
 from ssd_amd.model_config import ModelConfig, PRESETS  # noqa: E402
 from ssd_amd.utils.graphs import capture  # noqa: E402
 from ssd_amd.utils.topology import Topology  # noqa: E402
@@ -80,7 +80,7 @@ def probe(tp: int, M: int, grp, dev):
 
     print(f"==== TP = {tp}: per-rank shard of Llama-3.1-70B, M = {M} verify rows, ctx {ctx} ====")
     NL = 80
-    row(f"qkv+RoPE+KV store [{m.qkv_n}x{m.h}]", timed(lambda li: m.launch_qkv(li, M, r.d_pos, r.d_slots, pre_normed=True), L), m.qkv_n * m.h * 2 / 1e6, NL)
+    row(f"qkv+RoPE+KV store [{m.qkv_n}x{m.h}]", timed(lambda li: m.launch_qkv(li, M, r.d_pos, r.d_slots, src=NORMED), L), m.qkv_n * m.h * 2 / 1e6, NL)
     row(f"attention (nh {m.nh}, nkv {m.nkv}, {waves} waves, {splits} splits)",
         timed(lambda li: H.attn_paged(m.buf_q, m.kv_cache[li, 0], m.kv_cache[li, 1], meta.block_tables, m.max_blocks, meta.context_lens,
                                       1, M, M, m.nh, m.nkv, m.hd, m.block_size, scale, q_per_seq=M, mode=meta.mode, splits=splits,
@@ -89,7 +89,7 @@ def probe(tp: int, M: int, grp, dev):
     row("all-reduce + add + RMSNorm (1 rank: launch + flags only)",
         timed(lambda li: ar.all_reduce_add_rmsnorm(m.buf_h, m.buf_res, m.buf_res, w[f"model.layers.{li}.post_attention_layernorm.weight"],
                                                    eps, M, m.h, out_frag=m.buf_xf), L), M * m.h * 2 * 3 / 1e6, 2 * NL)
-    row(f"gate_up+SiLU [{2 * m.I}x{m.h}]", timed(lambda li: m.launch_gate_up(li, M, pre_normed=True), L), 2 * m.I * m.h * 2 / 1e6, NL)
+    row(f"gate_up+SiLU [{2 * m.I}x{m.h}]", timed(lambda li: m.launch_gate_up(li, M, src=NORMED), L), 2 * m.I * m.h * 2 / 1e6, NL)
     row(f"down_proj [{m.h}x{m.I}]", timed(lambda li: m.launch_down(li, M), L), m.h * m.I * 2 / 1e6, NL)
     row("embedding + all-reduce", timed(lambda li: (H.embedding(r.d_ids, w["model.embed_tokens.weight"], m.buf_h, M, m.h, vocab_start=0,
                                                                vocab_count=m.V), m._allreduce(m.buf_h[:M])), 4), 0.0, 1)

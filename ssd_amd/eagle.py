@@ -80,10 +80,7 @@ class HipEagleDraft(HipDecoder):
             H.rope_store_kv(self.buf_qkv, positions, self.cos_sin, meta.slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
                             self.hd, self.block_size, eps=cfg.rms_norm_eps, qkv_perm=1)
         splits, attn_waves = self._attn_cfg(T, meta)
-        H.attn_paged(self.buf_q, kc, vc, meta.block_tables, self.max_blocks, meta.context_lens, meta.B, T, meta.max_q, self.nh,
-                     self.nkv, self.hd, self.block_size, self.hd ** -0.5, cu_q=meta.cu_q, q_per_seq=meta.q_per_seq, mode=meta.mode,
-                     tree_K=meta.tree_K, tree_mq=meta.tree_mq, tree_step=meta.tree_step, tree_F=meta.tree_F, tree_jidx=meta.tree_jidx,
-                     splits=splits, ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=attn_waves)
+        self._attn(0, T, meta, splits, None, attn_waves, self.hd ** -0.5)
         self._gemm(self.buf_af, self.qn, w[p + "self_attn.o_proj.weight"], h, self.buf_h, T, h)
         # the CONDITIONING features, not the token embeddings, are the residual stream (:151-155)
         H.rmsnorm(self.buf_h, w[p + "post_attention_layernorm.weight"], cfg.rms_norm_eps, T, h, res_in=self.buf_cond,
@@ -91,7 +88,6 @@ class HipEagleDraft(HipDecoder):
         self._gemm(self.buf_xf, h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG)
         self._gemm(self.buf_actf, self.I, w[p + "mlp.down_proj.weight"], h, self.buf_h, T, h)
         torch.add(self.buf_h[:T], self.buf_res[:T], out=self.buf_pre[:T])          # eager bf16 add of the reference (:155)
-        self._last_parts = False
 
     def compute_logits(self, T: int, gather: torch.Tensor | None = None, rows: int | None = None) -> int:
         """final_norm + draft-vocabulary head, scattered to target-vocabulary columns of self.logits[:n] (:305-352)."""

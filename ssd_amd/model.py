@@ -13,6 +13,7 @@ hipGraph on ROCm) including the RCCL all-reduces.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import os
 
@@ -48,6 +49,18 @@ class AttnMeta:
     tree_F: int = 1
     tree_jidx: torch.Tensor | None = None
     ctx_hint: int = 0             # host-side upper bound of the context lengths (0 = unknown -> max_model_len)
+
+
+class Slabs(NamedTuple):
+    """Where a GEMM left its result when not as bf16 rows in buf_h (that hand-off is None): fp32 split-K slabs [n][rows][h], summed by
+    the consumer's norm -- buf_parts_o / buf_parts_d (ssd_gemm_parts, attention + o_proj) or the prefill workspace (PF_EPI_PARTIALS)."""
+    buf: torch.Tensor
+    n: int
+    rows: int
+
+
+NORMED = "normed"       # hand-off marker: the fused all-reduce + add + RMSNorm already left buf_xf / buf_res as the consumer's norm would
+_PLAN = "plan"          # default of launch_*(src=): the hand-off parts_plan(T) implies (the launches taken one by one: bench.py, probes)
 
 
 def make_cos_sin(head_dim: int, max_pos: int, theta: float, device) -> torch.Tensor:
@@ -201,7 +214,7 @@ class HipDecoder:
         if self.tree_seg:
             self.tree_ws = z(H.tree_segment_workspace_bytes(self.h, self.I) // 8, dtype=torch.int64)
             self.buf_res_b = z(min(T, 32), self.h)        # the residual ping-pongs: every workgroup re-reads a layer's input residual
-        self._last_parts = False        # set by forward() for the compute_logits that follows it
+        self._last: Slabs | None = None     # the last forward()'s hand-off, for the compute_logits that follows it
         pt = min(T, 32)
         self.buf_parts_o = z(16 * pt * self.h, dtype=torch.float32) if self.use_parts else None
         self.buf_parts_d = z(16 * pt * self.h, dtype=torch.float32) if self.use_parts else None
@@ -307,20 +320,22 @@ class HipDecoder:
                 self.w[name] = w
         torch.cuda.synchronize(self.device)
 
+    def _row_map(self, name: str, N: int) -> torch.Tensor | None:
+        """Source row of every packed row of a quantized [N, K] linear (QKV: rotation-paired, gate_up: interleaved), None = in order."""
+        if name.endswith("qkv_proj.weight"):
+            return quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
+        if name.endswith("gate_up_proj.weight"):
+            return quant.gate_up_row_map(N).to(self.device)
+        return None
+
     def _load_fp8(self, name: str, w) -> None:
         q, s = (w[0].to(self.device), w[1].to(self.device)) if isinstance(w, tuple) else quant.quantize_fp8(w.to(self.device))
         q, s = q.contiguous(), s.to(torch.float32).reshape(-1).contiguous()
         N, K = q.shape
         assert q.dtype == quant.FP8 and s.numel() == N, (name, q.dtype, s.shape)
-        if name.endswith("qkv_proj.weight"):
-            row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd)
-        elif name.endswith("gate_up_proj.weight"):
-            row_map = quant.gate_up_row_map(N)
-        else:
-            row_map = None
+        row_map = self._row_map(name, N)
         out = torch.empty(N * K, dtype=torch.uint8, device=self.device)
         if row_map is not None:
-            row_map = row_map.to(self.device)
             s = s[row_map.long()].contiguous()
         Q.fp8_rows_to_frag(q.view(torch.uint8), out, N, K, row_map=row_map)
         self.w[name] = out
@@ -336,12 +351,7 @@ class HipDecoder:
         if isinstance(w, quant.W4ZTensor):
             zero = w.zero.to(self.device).contiguous()
             assert zero.dtype == torch.uint8 and zero.shape == s.shape and int(zero.max()) <= 15, (name, zero.dtype, zero.shape)
-        if name.endswith("qkv_proj.weight"):
-            row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
-        elif name.endswith("gate_up_proj.weight"):
-            row_map = quant.gate_up_row_map(N).to(self.device)
-        else:
-            row_map = None
+        row_map = self._row_map(name, N)
         q_frag = torch.empty(N * K // 2, dtype=torch.uint8, device=self.device)
         s_frag = torch.empty(N * K // quant.W4_GROUP, dtype=BF16, device=self.device)
         if zero is not None:
@@ -362,12 +372,7 @@ class HipDecoder:
         N, K = packed.shape[0], packed.shape[1] * 2
         assert packed.dtype == torch.uint8 and tuple(s.shape) == (N, K // quant.MX4_BLOCK), (name, packed.dtype, s.shape)
         quant.check_mxfp4_scales(name, s)
-        if name.endswith("qkv_proj.weight"):
-            row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
-        elif name.endswith("gate_up_proj.weight"):
-            row_map = quant.gate_up_row_map(N).to(self.device)
-        else:
-            row_map = None
+        row_map = self._row_map(name, N)
         q_frag = torch.empty(N * K // 2, dtype=torch.uint8, device=self.device)
         s_frag = torch.empty(N * K // quant.MX4_BLOCK, dtype=torch.uint8, device=self.device)
         MX4.mx4_rows_to_frag(packed, s, q_frag, s_frag, N, K, row_map=row_map)
@@ -425,20 +430,22 @@ class HipDecoder:
         self.kv_scale.copy_(s)
         self.kv_inv_scale.copy_(1.0 / s)
 
-    def _attn(self, li: int, T: int, meta: AttnMeta, splits: int, flags: int, waves: int, scale: float) -> None:
-        """The layer's paged attention launch into buf_af, over the bf16 or the fp8 cache."""
+    def _attn(self, li: int, T: int, meta: AttnMeta, splits: int, flags: int | None, waves: int, scale: float) -> None:
+        """The layer's paged attention launch into buf_af, over the bf16 or the fp8 cache.  flags None: left to the kernel's default
+        (0: the chain / tree segments and the EAGLE-3 draft, which never take forward()'s _attn_flags)."""
+        fl = {} if flags is None else dict(flags=flags)
         if self.kv8:
             assert meta.mode == H.MODE_CAUSAL, "the fp8 KV cache serves the target's causal shapes only"
             KV8.attn_paged_fp8(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
                                meta.context_lens, meta.B, T, meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale,
                                k_scale=self.kv_scale[li, 0], v_scale=self.kv_scale[li, 1], cu_q=meta.cu_q, q_per_seq=meta.q_per_seq,
-                               splits=splits, flags=flags, ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=waves)
+                               splits=splits, ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=waves, **fl)
             return
         H.attn_paged(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
                      meta.context_lens, meta.B, T, meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale,
                      cu_q=meta.cu_q, q_per_seq=meta.q_per_seq, mode=meta.mode, tree_K=meta.tree_K, tree_mq=meta.tree_mq,
                      tree_step=meta.tree_step, tree_F=meta.tree_F, tree_jidx=meta.tree_jidx, splits=splits,
-                     flags=flags, ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=waves)
+                     ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=waves, **fl)
 
     # ---------------------------------------------------------------------------------------------
     PF_MIN_WEIGHT_BYTES = 100 << 20
@@ -482,16 +489,15 @@ class HipDecoder:
         """o_proj / down_proj of ONE prefill chunk may leave their split-K partials in the workspace for the norm that follows."""
         return self.pf_parts and not self.use_coll and 32 < T <= 128 and self._pf_eligible(N, K) and self._ws_pf is not None
 
-    @staticmethod
-    def _pf_splits(T: int, N: int, K: int) -> int:
-        return H.gemm_pf_workspace_bytes(T, N, K) // (4 * T * N)
-
-    def _gemm_pf_partials(self, xf, K, w, N, T) -> int:
-        """Prefill GEMM stopped after its split-K stage (csrc/gemm_pf.hip PF_EPI_PARTIALS): fp32 slabs [S][T][N] in the workspace;
-        returns S.  The consumer is ssd_rmsnorm_parts -- one launch per GEMM less."""
+    def _gemm_pf_partials(self, xf, K, w, N, T, min_splits: int = 1) -> Slabs | None:
+        """Prefill GEMM stopped after its split-K stage (csrc/gemm_pf.hip PF_EPI_PARTIALS): fp32 slabs [S][T][N] in the workspace, summed
+        by the consumer (ssd_rmsnorm_parts / ssd_rope_store_kv_parts) -- one launch per GEMM less.  Nothing is launched, and None
+        returned, where the decomposition has fewer than min_splits slabs."""
         S = H.gemm_pf_workspace_bytes(T, N, K) // (4 * T * N)
+        if S < min_splits:
+            return None
         H.gemm_pf(xf, w, None, T, N, K, N, self._ws_pf, epilogue=H.PF_EPI_PARTIALS)
-        return S
+        return Slabs(self._ws_pf, S, T)
 
     def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None, zero=None):
         if scale is not None and self.w4 and zero is not None:   # w4a16 codes (w) + group scales + group zero points
@@ -557,7 +563,10 @@ class HipDecoder:
         below 1K keys the extra launch costs more than it saves)."""
         G = self.nh // self.nkv
         row_tiles = -(-(meta.max_q * G) // 16)
-        groups = -(-row_tiles // 2) if row_tiles > 8 else row_tiles       # csrc/attention.hip attn_launch
+        # attn_launch's default of two row tiles per workgroup above 8 tiles.  _attn_flags launches those shapes with ONE tile per
+        # workgroup, so the real grid is twice this model's; the two-tile model is kept on purpose: it decides the wave split, and with
+        # the wave split the accumulation order -- the bit pattern -- of every prefill stays what it is
+        groups = -(-row_tiles // 2) if row_tiles > 8 else row_tiles
         base = max(1, groups * meta.B * self.nkv)
         waves = max(1, min(8, 512 // base))
         # (prefill with 4 / 8 waves per workgroup, measured on c4: TTFT 30.92 ms (this heuristic, 2 waves) / 30.68 / 30.74 -- within noise, and
@@ -641,23 +650,27 @@ class HipDecoder:
         return (self.chain_seg and T == 1 and meta.B == 1 and meta.cu_q is None and meta.mode == H.MODE_CAUSAL and splits == 1
                 and self.fusion_plan(T)[1] and "model.layers.0.self_attn.qkv_proj.bias" not in self.w)
 
+    def _next_qkv(self, li: int, positions, meta: AttnMeta, rows: bool = False) -> dict:
+        """What a chain / tree segment needs to run layer li's norm + QKV at its end: with RoPE + KV store, or (rows: the q / k norm
+        models) leaving raw QKV rows in buf_qkv."""
+        p = f"model.layers.{li}."
+        nxt = dict(w_qkv_next=self.w[p + "self_attn.qkv_proj.weight"], ln_next=self.w[p + "input_layernorm.weight"])
+        if rows:
+            return dict(nxt, qkv_rows_next=self.buf_qkv)
+        return dict(nxt, positions=positions, cos_sin=self.cos_sin, slots=meta.slot_mapping, q_out=self.buf_q,
+                    k_cache=self.kv_cache[li, 0], v_cache=self.kv_cache[li, 1])
+
     def _forward_chain(self, positions, meta: AttnMeta, attn_waves: int) -> None:
         cfg, w = self.cfg, self.w
         L = cfg.num_layers
         scale = self.hd ** -0.5
         H.chain_tick(self.chain_gen)
-        self.launch_qkv(0, 1, positions, meta.slot_mapping, parts=False)       # layer 0: norm(embedding) + QKV + RoPE + KV store
+        self.launch_qkv(0, 1, positions, meta.slot_mapping, src=None)       # layer 0: norm(embedding) + QKV + RoPE + KV store
         for li in range(L):
-            H.attn_paged(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
-                         meta.context_lens, meta.B, 1, meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale,
-                         cu_q=None, q_per_seq=meta.q_per_seq, mode=meta.mode, splits=1, ws_o=self.ws_o, ws_ml=self.ws_ml,
-                         out_frag=self.buf_af, waves=attn_waves)
+            self._attn(li, 1, meta, 1, None, attn_waves, scale)
             p = f"model.layers.{li}."
             last = li + 1 == L
-            nxt = {} if last else dict(
-                w_qkv_next=w[f"model.layers.{li + 1}.self_attn.qkv_proj.weight"], ln_next=w[f"model.layers.{li + 1}.input_layernorm.weight"],
-                positions=positions, cos_sin=self.cos_sin, slots=meta.slot_mapping, q_out=self.buf_q,
-                k_cache=self.kv_cache[li + 1, 0], v_cache=self.kv_cache[li + 1, 1])
+            nxt = {} if last else self._next_qkv(li + 1, positions, meta)
             rin, rout = (self.buf_res2, self.buf_res3) if li % 2 == 0 else (self.buf_res3, self.buf_res2)
             H.chain_segment(self.buf_af, rin, self.buf_res if last else rout, w[p + "self_attn.o_proj.weight"],
                             w[p + "mlp.gate_up_proj.weight"], w[p + "mlp.down_proj.weight"], w[p + "post_attention_layernorm.weight"],
@@ -692,134 +705,123 @@ class HipDecoder:
                 H.rope_store_kv(self.buf_qkv, positions, self.cos_sin, meta.slot_mapping, self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1],
                                 T, self.nh, self.nkv, self.hd, self.block_size, q_norm_w=w[p_ + "q_norm.weight"],
                                 k_norm_w=w[p_ + "k_norm.weight"], eps=cfg.rms_norm_eps, qkv_perm=1)
-            H.attn_paged(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
-                         meta.context_lens, meta.B, T, meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale,
-                         cu_q=None, q_per_seq=meta.q_per_seq, mode=meta.mode, tree_K=meta.tree_K, tree_mq=meta.tree_mq,
-                         tree_step=meta.tree_step, tree_F=meta.tree_F, tree_jidx=meta.tree_jidx, splits=splits,
-                         ws_o=self.ws_o, ws_ml=self.ws_ml, out_frag=self.buf_af, waves=attn_waves)
+            self._attn(li, T, meta, splits, None, attn_waves, scale)       # (never forward()'s _attn_flags: not 0 at 24 rows with G = 16)
             p = f"model.layers.{li}."
             last = li + 1 == L
-            nxt = {} if last else dict(
-                w_qkv_next=w[f"model.layers.{li + 1}.self_attn.qkv_proj.weight"], ln_next=w[f"model.layers.{li + 1}.input_layernorm.weight"],
-                qkv_rows_next=self.buf_qkv) if qk else dict(
-                w_qkv_next=w[f"model.layers.{li + 1}.self_attn.qkv_proj.weight"], ln_next=w[f"model.layers.{li + 1}.input_layernorm.weight"],
-                positions=positions, cos_sin=self.cos_sin, slots=meta.slot_mapping, q_out=self.buf_q,
-                k_cache=self.kv_cache[li + 1, 0], v_cache=self.kv_cache[li + 1, 1])
+            nxt = {} if last else self._next_qkv(li + 1, positions, meta, rows=qk)
             H.tree_segment(self.buf_af, res[(start + li) % 2], res[(start + li + 1) % 2], w[p + "self_attn.o_proj.weight"],
                            w[p + "mlp.gate_up_proj.weight"], w[p + "mlp.down_proj.weight"], w[p + "post_attention_layernorm.weight"],
                            cfg.rms_norm_eps, T, self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd, self.block_size, li,
                            self.tree_ws, self.chain_gen, self.chain_err, h_out=self.buf_h if last else None, **nxt)
 
-    def launch_qkv(self, li: int, T: int, positions, slot_mapping, gemm_only: bool = False, pre_normed: bool = False,
-                   parts: bool | None = None, pf_src: int = 0) -> None:
+    # ---- the hand-off between two launches: where the previous GEMM left the hidden state.  None = bf16 rows in buf_h, a Slabs = fp32
+    # split-K slabs the consumer's norm sums, NORMED = the fused all-reduce + add + RMSNorm has already done the consumer's norm.
+    # launch_o / launch_down (and the fused attention + o_proj) return it, launch_qkv / launch_gate_up take it as src=, forward()
+    # threads it through the layers and keeps the last one for compute_logits.
+    def _plan_src(self, which: str, T: int) -> Slabs | None:
+        """The hand-off launch_o ("o") / launch_down ("d") leave at T rows when nobody says otherwise."""
+        if not self.parts_plan(T):
+            return None
+        return Slabs(self.buf_parts_o if which == "o" else self.buf_parts_d, self._parts(which, T)[0], T)
+
+    def _add_norm(self, src, T: int, weight, **kw) -> None:
+        """Residual add + RMSNorm of the hidden state the hand-off `src` describes; kw: res_in / res_out / out_frag of the norm kernels,
+        and gather (rows only), passed on as given."""
+        if src is NORMED:
+            return
+        if src is None:
+            H.rmsnorm(self.buf_h, weight, self.cfg.rms_norm_eps, T, self.h, **kw)
+            return
+        assert kw.pop("gather", None) is None and T == src.rows
+        H.rmsnorm_parts(src.buf, src.n, src.rows, weight, self.cfg.rms_norm_eps, T, self.h, **kw)
+
+    def _prologue_src(self, src) -> dict:
+        """The same hand-off as the input of a norm-fused GEMM prologue (csrc/gemm_fused.hip)."""
+        return dict(h_rows=self.buf_h) if src is None else dict(h_parts=src.buf, splits=src.n)
+
+    def launch_qkv(self, li: int, T: int, positions, slot_mapping, gemm_only: bool = False, src=_PLAN) -> None:
         """gemm_only: skip the separate add+RMSNorm / RoPE launches of the unfused variants (kernel timing).
-        pre_normed: buf_xf / buf_res already hold this layer's normalised input and residual (written by the fused
-        all-reduce + add + RMSNorm that closed the previous layer)."""
+        src: the hand-off of the previous layer's down_proj (layer 0: None, the embedding rows)."""
         cfg, w = self.cfg, self.w
         p = f"model.layers.{li}."
         small, norm_fuse = self.fusion_plan(T)
         kc, vc = self.kv_cache[li, 0], self.kv_cache[li, 1]
         rope = dict(positions=positions, cos_sin=self.cos_sin, slots=slot_mapping, q_out=self.buf_q, k_cache=kc, v_cache=vc,
                     nh=self.nh, nkv=self.nkv, hd=self.hd, block_size=self.block_size)
-        h, res, xf = self.buf_h, self.buf_res, self.buf_xf
-        parts = (self.parts_plan(T) if parts is None else parts) and li > 0   # the previous layer's down_proj left fp32 slabs, not rows
-        if norm_fuse:
-            src = dict(h_parts=self.buf_parts_d, splits=self._parts("d", T)[0]) if parts else dict(h_rows=h)
-            H.gemm_fused(w[p + "self_attn.qkv_proj.weight"], T, self.qkv_n, self.h, H.FEPI_QKV_ROPE,
-                         res_in=None if li == 0 else res, res_out=self.buf_res2, norm_w=w[p + "input_layernorm.weight"],
-                         eps=cfg.rms_norm_eps, bias=w.get(p + "self_attn.qkv_proj.bias"), waves=16, **src, **rope)
-            return
+        res, xf = self.buf_res, self.buf_xf
+        wq, bias = w[p + "self_attn.qkv_proj.weight"], w.get(p + "self_attn.qkv_proj.bias")
+        if src is _PLAN:
+            src = self._plan_src("d", T) if li > 0 else None
         # residual is None on layer 0 (llama3.py:187-190): residual := embeddings, x := norm(embeddings)
-        if not gemm_only and not pre_normed:
-            if pf_src:       # the previous layer's down_proj left pf_src split-K slabs [pf_src][T][h] in the prefill workspace
-                H.rmsnorm_parts(self._ws_pf, pf_src, T, w[p + "input_layernorm.weight"], cfg.rms_norm_eps, T, self.h,
-                                res_in=res, res_out=res, out_frag=xf)
-            elif parts:
-                H.rmsnorm_parts(self.buf_parts_d, self._parts("d", T)[0], T, w[p + "input_layernorm.weight"], cfg.rms_norm_eps, T, self.h,
-                                res_in=res, res_out=res, out_frag=xf)
-            else:
-                H.rmsnorm(h, w[p + "input_layernorm.weight"], cfg.rms_norm_eps, T, self.h, res_in=None if li == 0 else res,
-                          res_out=res, out_frag=xf)
+        res_in = None if li == 0 else res
+        if norm_fuse:
+            H.gemm_fused(wq, T, self.qkv_n, self.h, H.FEPI_QKV_ROPE, res_in=res_in, res_out=self.buf_res2, norm_w=w[p + "input_layernorm.weight"],
+                         eps=cfg.rms_norm_eps, bias=bias, waves=16, **self._prologue_src(src), **rope)
+            return
+        if not gemm_only:
+            self._add_norm(src, T, w[p + "input_layernorm.weight"], res_in=res_in, res_out=res, out_frag=xf)
         if small or (16 < T <= 32 and not cfg.qk_norm and not self.quantized and not self.kv8):      # T in 17..32 (tree-decode step): the two-token-tile variant
-            H.gemm_fused(w[p + "self_attn.qkv_proj.weight"], T, self.qkv_n, self.h, H.FEPI_QKV_ROPE, x_frag=xf,
-                         bias=w.get(p + "self_attn.qkv_proj.bias"), **rope)
-        elif (not gemm_only and not self.kv8 and w.get(p + "self_attn.qkv_proj.bias") is None and self._pf_partials_ok(T, self.qkv_n, self.h)
-              and self._pf_splits(T, self.qkv_n, self.h) > 1):
+            H.gemm_fused(wq, T, self.qkv_n, self.h, H.FEPI_QKV_ROPE, x_frag=xf, bias=bias, **rope)
+            return
+        head_norm = dict(q_norm_w=w.get(p + "self_attn.q_norm.weight"), k_norm_w=w.get(p + "self_attn.k_norm.weight"), eps=cfg.rms_norm_eps,
+                         qkv_perm=1)
+        if not gemm_only and not self.kv8 and bias is None and self._pf_partials_ok(T, self.qkv_n, self.h):
             # single-chunk prefill of a big QKV matrix: its split-K slabs stay in the workspace and the RoPE / KV-store kernel
             # sums them (bit-identical to the GEMM's epilogue launch + rope_store_kv; one launch less per layer)
-            S = self._gemm_pf_partials(xf, self.h, w[p + "self_attn.qkv_proj.weight"], self.qkv_n, T)
-            H.rope_store_kv_parts(self._ws_pf, S, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
-                                  self.hd, self.block_size, q_norm_w=w.get(p + "self_attn.q_norm.weight"),
-                                  k_norm_w=w.get(p + "self_attn.k_norm.weight"), eps=cfg.rms_norm_eps, qkv_perm=1)
-        else:
-            self._gemm(xf, self.h, w[p + "self_attn.qkv_proj.weight"], self.qkv_n, self.buf_qkv, T, self.qkv_n,
-                       bias=w.get(p + "self_attn.qkv_proj.bias"), scale=w.get(p + "self_attn.qkv_proj.weight_scale"),
-                       zero=w.get(p + "self_attn.qkv_proj.weight_zero"))
-            if gemm_only:
+            qkv = self._gemm_pf_partials(xf, self.h, wq, self.qkv_n, T, min_splits=2)
+            if qkv is not None:
+                H.rope_store_kv_parts(qkv.buf, qkv.n, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
+                                      self.hd, self.block_size, **head_norm)
                 return
-            if self.kv8:
-                KV8.rope_store_kv_fp8(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
-                                      self.hd, self.block_size, k_inv_scale=self.kv_inv_scale[li, 0], v_inv_scale=self.kv_inv_scale[li, 1],
-                                      q_norm_w=w.get(p + "self_attn.q_norm.weight"), k_norm_w=w.get(p + "self_attn.k_norm.weight"),
-                                      eps=cfg.rms_norm_eps, qkv_perm=1)
-                return
-            H.rope_store_kv(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
-                            self.hd, self.block_size, q_norm_w=w.get(p + "self_attn.q_norm.weight"),
-                            k_norm_w=w.get(p + "self_attn.k_norm.weight"), eps=cfg.rms_norm_eps, qkv_perm=1)
+        self._gemm(xf, self.h, wq, self.qkv_n, self.buf_qkv, T, self.qkv_n, bias=bias, scale=w.get(p + "self_attn.qkv_proj.weight_scale"),
+                   zero=w.get(p + "self_attn.qkv_proj.weight_zero"))
+        if gemm_only:
+            return
+        if self.kv8:
+            KV8.rope_store_kv_fp8(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
+                                  self.hd, self.block_size, k_inv_scale=self.kv_inv_scale[li, 0], v_inv_scale=self.kv_inv_scale[li, 1],
+                                  **head_norm)
+            return
+        H.rope_store_kv(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
+                        self.hd, self.block_size, **head_norm)
 
-    def launch_o(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> int:
-        """Returns the number of split-K slabs left in the prefill workspace (pf_partials), else 0."""
-        w = self.w[f"model.layers.{li}.self_attn.o_proj.weight"]
-        ws = self.w.get(f"model.layers.{li}.self_attn.o_proj.weight_scale")
-        if pf_partials and self._pf_partials_ok(T, self.h, self.qn):
-            return self._gemm_pf_partials(self.buf_af, self.qn, w, self.h, T)
+    def _launch_to_h(self, which: str, li: int, T: int, parts: bool | None, pf_partials: bool) -> Slabs | None:
+        """o_proj ("o") / down_proj ("d"): the [h, K] GEMM whose result the next norm reads.  Returns the hand-off: the prefill GEMM's
+        split-K slabs in the workspace (pf_partials, one prefill chunk of a big matrix), ssd_gemm_parts' slabs (parts; None: as
+        parts_plan says), or None for rows in buf_h."""
+        name, xf, K, slabs = ((f"model.layers.{li}.self_attn.o_proj.weight", self.buf_af, self.qn, self.buf_parts_o) if which == "o" else
+                              (f"model.layers.{li}.mlp.down_proj.weight", self.buf_actf, self.I, self.buf_parts_d))
+        w = self.w[name]
+        if pf_partials and self._pf_partials_ok(T, self.h, K):
+            return self._gemm_pf_partials(xf, K, w, self.h, T)
         if self.parts_plan(T) if parts is None else parts:
-            S, wv = self._parts("o", T)
-            H.gemm_parts(self.buf_af, w, T, self.h, self.qn, parts=self.buf_parts_o, splits=S, waves=wv)
-        else:
-            self._gemm(self.buf_af, self.qn, w, self.h, self.buf_h, T, self.h, scale=ws,
-                       zero=self.w.get(f"model.layers.{li}.self_attn.o_proj.weight_zero"))
-        return 0
+            S, wv = self._parts(which, T)
+            H.gemm_parts(xf, w, T, self.h, K, parts=slabs, splits=S, waves=wv)
+            return Slabs(slabs, S, T)
+        self._gemm(xf, K, w, self.h, self.buf_h, T, self.h, scale=self.w.get(name + "_scale"), zero=self.w.get(name + "_zero"))
+        return None
 
-    def launch_gate_up(self, li: int, T: int, gemm_only: bool = False, pre_normed: bool = False, parts: bool | None = None,
-                       o_splits: int | None = None, pf_src: int = 0) -> None:
-        """o_splits: slabs o_proj left in buf_parts_o (default: the split-K GEMM's; the fused attention + o_proj leaves nkv)."""
+    def launch_o(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> Slabs | None:
+        return self._launch_to_h("o", li, T, parts, pf_partials)
+
+    def launch_gate_up(self, li: int, T: int, gemm_only: bool = False, src=_PLAN) -> None:
+        """src: the hand-off of o_proj (the split-K GEMM leaves its own number of slabs, the fused attention + o_proj nkv)."""
         cfg, w = self.cfg, self.w
         p = f"model.layers.{li}."
-        _, norm_fuse = self.fusion_plan(T)
-        parts = self.parts_plan(T) if parts is None else parts      # o_proj left fp32 partial slabs
-        So = o_splits if o_splits is not None else (self._parts("o", T)[0] if parts else 1)
-        if norm_fuse:
-            src = dict(h_parts=self.buf_parts_o, splits=So) if parts else dict(h_rows=self.buf_h)
+        if src is _PLAN:
+            src = self._plan_src("o", T)
+        if self.fusion_plan(T)[1]:
             H.gemm_fused(w[p + "mlp.gate_up_proj.weight"], T, 2 * self.I, self.h, H.FEPI_SILU_FRAG,
                          res_in=self.buf_res2, res_out=self.buf_res, norm_w=w[p + "post_attention_layernorm.weight"],
-                         eps=cfg.rms_norm_eps, y=self.buf_actf, waves=8, **src)     # profiles/micro/fused_probe.py: 13.2 us vs 16.4 (16 waves)
-        else:
-            if not gemm_only and not pre_normed:
-                if pf_src:       # o_proj left pf_src split-K slabs in the prefill workspace
-                    H.rmsnorm_parts(self._ws_pf, pf_src, T, w[p + "post_attention_layernorm.weight"], cfg.rms_norm_eps,
-                                    T, self.h, res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
-                elif parts:
-                    H.rmsnorm_parts(self.buf_parts_o, So, T, w[p + "post_attention_layernorm.weight"], cfg.rms_norm_eps,
-                                    T, self.h, res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
-                else:
-                    H.rmsnorm(self.buf_h, w[p + "post_attention_layernorm.weight"], cfg.rms_norm_eps, T, self.h,
-                              res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
-            self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG,
-                       scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"))
+                         eps=cfg.rms_norm_eps, y=self.buf_actf, waves=8, **self._prologue_src(src))     # profiles/micro/fused_probe.py: 13.2 us vs 16.4 (16 waves)
+            return
+        if not gemm_only:
+            self._add_norm(src, T, w[p + "post_attention_layernorm.weight"], res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
+        self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG,
+                   scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"))
 
-    def launch_down(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> int:
-        w = self.w[f"model.layers.{li}.mlp.down_proj.weight"]
-        ws = self.w.get(f"model.layers.{li}.mlp.down_proj.weight_scale")
-        if pf_partials and self._pf_partials_ok(T, self.h, self.I):
-            return self._gemm_pf_partials(self.buf_actf, self.I, w, self.h, T)
-        if self.parts_plan(T) if parts is None else parts:
-            S, wv = self._parts("d", T)
-            H.gemm_parts(self.buf_actf, w, T, self.h, self.I, parts=self.buf_parts_d, splits=S, waves=wv)
-        else:
-            self._gemm(self.buf_actf, self.I, w, self.h, self.buf_h, T, self.h, scale=ws,
-                       zero=self.w.get(f"model.layers.{li}.mlp.down_proj.weight_zero"))
-        return 0
+    def launch_down(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> Slabs | None:
+        return self._launch_to_h("d", li, T, parts, pf_partials)
 
     def forward(self, input_ids: torch.Tensor, positions: torch.Tensor, T: int, meta: AttnMeta) -> None:
         """Runs all layers; leaves the final (pre-norm) hidden state in buf_h and the residual in buf_res."""
@@ -831,18 +833,17 @@ class HipDecoder:
         splits, attn_waves = self._attn_cfg(T, meta)
         attn_flags = self._attn_flags(meta)
         scale = self.hd ** -0.5
-        # a varlen prefill never takes the slab path (its last-token gather reads rows); compute_logits, which always follows
-        # in the same Python body, must know whether the last down_proj left rows or partial slabs
-        parts = self.parts_plan(T) and meta.cu_q is None
-        self._fwd_T, self._last_parts = T, parts
+        # compute_logits, which always follows in the same Python body, reads the last hand-off: the segments leave rows (buf_h) + the
+        # residual (buf_res)
+        self._last = None
         if self.chain_plan(T, meta, splits):
-            self._last_parts = False            # the last segment leaves rows (buf_h) + the residual (buf_res) for compute_logits
             self._forward_chain(positions, meta, attn_waves)
             return
         if self.tree_plan(T, meta):
-            self._last_parts = False            # rows (buf_h) + the residual (buf_res), as above
             self._forward_tree_seg(positions, T, meta, splits, attn_waves)
             return
+        # a varlen prefill never takes the slab path (its last-token gather reads rows)
+        parts = self.parts_plan(T) and meta.cu_q is None
         fuse_ao = parts and self.attn_o_plan(T, meta, splits)
         # tensor parallel with the one-shot collective: the all-reduce after o_proj / down_proj absorbs the residual add
         # and the RMSNorm that follow it (csrc/comm.hip), 2 launches fewer per half layer
@@ -850,46 +851,44 @@ class HipDecoder:
         fuse = self.use_coll and ar is not None and self.fuse_ar_norm and ar.fits_rows(T, self.h)
         eps, res, xf = cfg.rms_norm_eps, self.buf_res, self.buf_xf
         L = cfg.num_layers
-        pf_d = 0            # split-K slabs the previous layer's down_proj left for this layer's input norm (single-chunk prefill)
+        src = None          # the hand-off: the embedding is rows in buf_h
         for li in range(L):
-            self.launch_qkv(li, T, positions, meta.slot_mapping, pre_normed=fuse and li > 0, parts=parts, pf_src=pf_d)
+            self.launch_qkv(li, T, positions, meta.slot_mapping, src=src)
             if self.taps is not None and li in self.taps:
                 # launch_qkv has just written x + residual: to buf_res2 on the fused-prologue path, to buf_res otherwise
-                src = self.buf_res2 if self.fusion_plan(T)[1] else res
+                tap = self.buf_res2 if self.fusion_plan(T)[1] else res
                 i = self.taps.index(li)
-                self.acts[:T, i * self.h:(i + 1) * self.h].copy_(src[:T])
-            pf_o = 0
+                self.acts[:T, i * self.h:(i + 1) * self.h].copy_(tap[:T])
             if fuse_ao:
                 H.attn_oproj_parts(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
                                    meta.context_lens, T, self.nh, self.nkv, self.hd, self.block_size, scale,
                                    w[f"model.layers.{li}.self_attn.o_proj.weight"], self.h, self.buf_parts_o)
+                src = Slabs(self.buf_parts_o, self.nkv, T)
             else:
                 self._attn(li, T, meta, splits, attn_flags, attn_waves, scale)
-                pf_o = self.launch_o(li, T, parts=parts, pf_partials=not parts)
+                src = self.launch_o(li, T, parts=parts, pf_partials=not parts)
             if fuse:
                 ar.all_reduce_add_rmsnorm(h, res, res, w[f"model.layers.{li}.post_attention_layernorm.weight"], eps, T, self.h, out_frag=xf)
+                src = NORMED
             else:
                 self._allreduce(h[:T])
-            self.launch_gate_up(li, T, pre_normed=fuse, parts=parts, o_splits=self.nkv if fuse_ao else None, pf_src=pf_o)
+            self.launch_gate_up(li, T, src=src)
             # (the last layer's down_proj keeps its epilogue: compute_logits' last-token gather reads rows)
-            pf_d = self.launch_down(li, T, parts=parts, pf_partials=not parts and li + 1 < L)
+            src = self.launch_down(li, T, parts=parts, pf_partials=not parts and li + 1 < L)
             if fuse and li + 1 < L:
                 ar.all_reduce_add_rmsnorm(h, res, res, w[f"model.layers.{li + 1}.input_layernorm.weight"], eps, T, self.h, out_frag=xf)
+                src = NORMED
             else:
                 self._allreduce(h[:T])
+        self._last = src
+
 
     def compute_logits(self, T: int, gather: torch.Tensor | None = None, rows: int | None = None) -> int:
         """Final add+RMSNorm (optionally only the `gather` rows: prefill last-token, embed_head.py:81-84) and the
         LM-head GEMM into self.logits[:rows] (this rank's vocab shard).  Returns the number of logit rows."""
         n = T if gather is None else rows
         assert n <= self.max_logit_rows
-        if self._last_parts:
-            assert gather is None and n == self._fwd_T
-            H.rmsnorm_parts(self.buf_parts_d, self._parts("d", n)[0], n, self.w["model.norm.weight"], self.cfg.rms_norm_eps, n, self.h,
-                            res_in=self.buf_res, out_frag=self.buf_lastf)
-        else:
-            H.rmsnorm(self.buf_h, self.w["model.norm.weight"], self.cfg.rms_norm_eps, n, self.h, res_in=self.buf_res,
-                      out_frag=self.buf_lastf, gather=gather)
+        self._add_norm(self._last, n, self.w["model.norm.weight"], res_in=self.buf_res, out_frag=self.buf_lastf, gather=gather)
         if self._ap_ok(n):
             H.gemm_argmax(self.buf_lastf, self.w["lm_head.weight"], self.logits, n, self.V, self.h, self.V, self.ap_val, self.ap_idx,
                           self.ap_stride)
@@ -925,46 +924,40 @@ class HipDecoder:
                out3_stride: int = 0) -> None:
         """Greedy tokens of logits[:n] over the FULL vocabulary (identical on every TP rank).  out3 (optional): a third
         destination written with a row stride (the tree step's [T][K] token table; only with candidates available)."""
-        if self._ap_ok(n):          # candidates from the LM-head epilogue: a few thousand per row instead of V logits
-            np_ = self._ap_parts(n)
-            if not self.use_coll:
-                H.argmax_parts(self.ap_val, self.ap_idx, np_, self.ap_stride, n, out, out2, out3, out3_stride)
-                return
-            assert out3 is None
-            R = self.max_logit_rows
-            if self.custom_ar is not None:
-                idx_l = self.am_pack_l[:R]
-                val_l = self.am_pack_l[R:].view(torch.float32)[:R]
-                H.argmax_parts(self.ap_val, self.ap_idx, np_, self.ap_stride, n, idx_l, out_val=val_l, idx_offset=self.tp_rank * self.V)
-                self.custom_ar.all_gather_words(self.am_pack_l, self.am_pack, self.am_words)
-                vals = self.am_pack.view(-1)[R:].view(torch.float32)
-                H.argmax_merge(vals, self.am_pack, self.tp_size, n, 2 * self.am_words, out, out2, stride_idx=self.am_words)
-                return
-            H.argmax_parts(self.ap_val, self.ap_idx, np_, self.ap_stride, n, self.am_idx_l, out_val=self.am_val_l,
-                           idx_offset=self.tp_rank * self.V)
-            dist.all_gather_into_tensor(self.am_val.view(-1), self.am_val_l, group=self.tp_group)
-            dist.all_gather_into_tensor(self.am_idx.view(-1), self.am_idx_l, group=self.tp_group)
-            H.argmax_merge(self.am_val, self.am_idx, self.tp_size, n, R, out, out2)
+        if not self.use_coll:
+            if self._ap_ok(n):          # candidates from the LM-head epilogue: a few thousand per row instead of V logits
+                H.argmax_parts(self.ap_val, self.ap_idx, self._ap_parts(n), self.ap_stride, n, out, out2, out3, out3_stride)
+            else:
+                assert out3 is None
+                H.argmax_rows(self.logits, self.V, n, self.V, out, out2)
             return
         assert out3 is None
-        if not self.use_coll:
-            H.argmax_rows(self.logits, self.V, n, self.V, out, out2)
-            return
         R = self.max_logit_rows
-        if self.custom_ar is not None:
-            # local (value, global index) straight into the packed buffer, one one-shot all-gather, merge
-            idx_l = self.am_pack_l[:R]
-            val_l = self.am_pack_l[R:].view(torch.float32)[:R]
+        # one-shot exchange: local (global index, value) straight into this rank's packed buffer; else the two gather sources
+        packed = self.custom_ar is not None
+        idx_l, val_l = (self.am_pack_l[:R], self.am_pack_l[R:].view(torch.float32)[:R]) if packed else (self.am_idx_l, self.am_val_l)
+        self._argmax_local(n, idx_l, val_l)
+        self._argmax_merge(n, out, out2, packed)
+
+    def _argmax_local(self, n: int, idx_l, val_l) -> None:
+        """This rank's best (global index, value) per row of logits[:n]: from the LM-head candidates, else from the logits."""
+        if self._ap_ok(n):
+            H.argmax_parts(self.ap_val, self.ap_idx, self._ap_parts(n), self.ap_stride, n, idx_l, out_val=val_l, idx_offset=self.tp_rank * self.V)
+        else:
             H.argmax_rows_val(self.logits, self.V, n, self.V, self.tp_rank * self.V, idx_l, val_l)
+
+    def _argmax_merge(self, n: int, out, out2, packed: bool) -> None:
+        """Every rank's local best -> the winner per row, on every rank: one one-shot all-gather of the packed buffers (rank r's indices
+        start at word r * am_words, its values R words later: one strided merge), or two torch.distributed all-gathers into [tp][R]
+        (rows beyond n are ignored by the merge: T = n, stride R)."""
+        R = self.max_logit_rows
+        if packed:
             self.custom_ar.all_gather_words(self.am_pack_l, self.am_pack, self.am_words)
-            # rank r's indices start at word r*am_words, its values R words later: one strided merge
             vals = self.am_pack.view(-1)[R:].view(torch.float32)
             H.argmax_merge(vals, self.am_pack, self.tp_size, n, 2 * self.am_words, out, out2, stride_idx=self.am_words)
             return
-        H.argmax_rows_val(self.logits, self.V, n, self.V, self.tp_rank * self.V, self.am_idx_l, self.am_val_l)
         dist.all_gather_into_tensor(self.am_val.view(-1), self.am_val_l, group=self.tp_group)
         dist.all_gather_into_tensor(self.am_idx.view(-1), self.am_idx_l, group=self.tp_group)
-        # gathered layout is [tp][R]; rows beyond n are ignored by the merge (T = n, stride R)
         H.argmax_merge(self.am_val, self.am_idx, self.tp_size, n, R, out, out2)
 
     def full_logits(self, n: int) -> torch.Tensor:
