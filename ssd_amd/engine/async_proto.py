@@ -10,6 +10,8 @@ three-plus-logits:
                 draft block tables[B, max_blocks] (-1 padded) | temperature bits[B]
                 + top_k[B] | top_p bits[B] | min_p bits[B] at the very end, only when flags & FLAG_FILTER (some sequence of
                 the batch has a logit filter: the draft truncates its q as the target truncates its p)
+                + seed[B] (-1 = none) behind everything else, only when flags & FLAG_SEED (some sequence of the batch has a
+                seed: the draft draws that sequence's tokens from its own stream, include/ssd_hip_seed.h)
      prefill:   token ids (all sequences, concatenated) | num_tokens[B] | draft block tables[B, max_blocks]
   reply (speculate only) int64[B + B*K] = cache_hits[B] | tokens[B,K]
      + bf16 logits_q[B,K,V] only when flags & FLAG_WANT_LOGITS (some temperature > 0): at temperature 0 verify()
@@ -37,6 +39,7 @@ CMD_SPECULATE, CMD_PREFILL, CMD_EXIT, CMD_HELLO = 0, 1, 2, 3
 FLAG_WANT_LOGITS = 1
 FLAG_EAGLE = 2
 FLAG_FILTER = 4
+FLAG_SEED = 8
 HEADER_LEN = 4
 
 
@@ -50,8 +53,9 @@ def bits_temp(b: int) -> float:
 
 def pack_speculate(keys: list[tuple[int, int, int]], num_tokens: list[int], block_tables: list[list[int]],
                    temps: list[float], max_blocks: int, extend_counts: list[int] | None = None,
-                   extend_ids: list[list[int]] | None = None, *, filters=None) -> list[int]:
-    """filters: None (the payload is exactly the one without the feature) or (top_k [B], top_p [B], min_p [B])."""
+                   extend_ids: list[list[int]] | None = None, *, filters=None, seeds=None) -> list[int]:
+    """filters: None (the payload is exactly the one without the feature) or (top_k [B], top_p [B], min_p [B]).
+    seeds: None (likewise) or [B] integers in [-1, 2**63), -1 = the sequence has none."""
     out: list[int] = []
     for k in keys:
         out.extend(k)
@@ -69,18 +73,23 @@ def pack_speculate(keys: list[tuple[int, int, int]], num_tokens: list[int], bloc
         out.extend(int(k) for k in top_k)
         out.extend(temp_bits(p) for p in top_p)
         out.extend(temp_bits(m) for m in min_p)
+    if seeds is not None:
+        out.extend(int(x) for x in seeds)
     return out
 
 
-def unpack_speculate(payload: list[int], B: int, max_blocks: int, K: int | None = None, *, filters: bool = False):
+def unpack_speculate(payload: list[int], B: int, max_blocks: int, K: int | None = None, *, filters: bool = False, seeds: bool = False):
     """K given: the payload carries the EAGLE extend block; returns two more values (counts [B], ids [B][K]).
     filters=True (flags & FLAG_FILTER): the payload ends in the filter block; returns one more value, the tuple
-    (top_k [B], top_p [B], min_p [B])."""
+    (top_k [B], top_p [B], min_p [B]).  seeds=True (flags & FLAG_SEED): behind that the seed block; returns one more value, [B]."""
     tail = ()
+    if seeds:
+        tail = ([int(x) for x in payload[len(payload) - B:]],)
+        payload = payload[:len(payload) - B]
     if filters:
         blk = payload[len(payload) - 3 * B:]
         payload = payload[:len(payload) - 3 * B]
-        tail = (([int(k) for k in blk[:B]], [bits_temp(x) for x in blk[B:2 * B]], [bits_temp(x) for x in blk[2 * B:]]),)
+        tail = (([int(k) for k in blk[:B]], [bits_temp(x) for x in blk[B:2 * B]], [bits_temp(x) for x in blk[2 * B:]]),) + tail
     off = 0
     keys = [tuple(payload[off + 3 * b: off + 3 * b + 3]) for b in range(B)]
     off += 3 * B

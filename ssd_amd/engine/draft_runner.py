@@ -186,9 +186,9 @@ class DraftServer:
         dp = self.dp
         lead = dp is None or dp.rank == 0
         eagle = None
-        has_f = bool(flags & P.FLAG_FILTER)
+        has_f, has_s = bool(flags & P.FLAG_FILTER), bool(flags & P.FLAG_SEED)
         if flags & P.FLAG_EAGLE:
-            keys, num_tokens, tables, temps, ext_counts, ext_ids, *rest = P.unpack_speculate(payload, B, self.max_blocks, K, filters=has_f)
+            keys, num_tokens, tables, temps, ext_counts, ext_ids, *rest = P.unpack_speculate(payload, B, self.max_blocks, K, filters=has_f, seeds=has_s)
             cfg = self.runner.cfg
             acts = self.tx.recv_tensor((B, K + 1, cfg.eagle_taps * cfg.d_model_target), torch.bfloat16)
             # every draft position is one behind the sequence (pos_offset = -1, draft_runner.py:133-135,409,497): the
@@ -196,10 +196,15 @@ class DraftServer:
             num_tokens = [n - 1 for n in num_tokens]
             eagle = dict(acts=acts, ext_counts=ext_counts, ext_ids=ext_ids)
         else:
-            keys, num_tokens, tables, temps, *rest = P.unpack_speculate(payload, B, self.max_blocks, filters=has_f)
+            keys, num_tokens, tables, temps, *rest = P.unpack_speculate(payload, B, self.max_blocks, filters=has_f, seeds=has_s)
         # the request's logit filters reach the runner as a keyword, and only when the block is there: runners without the feature
         # (the oracle runners of the CPU tests, EAGLE-3 drafts) are never called with it
-        fkw = {"filters": rest[0]} if (rest and eagle is None) else {}
+        fkw = {}
+        if eagle is None:       # (the seed block, when there, is the last value)
+            if has_f:
+                fkw["filters"] = rest[0]
+            if has_s:
+                fkw["seeds"] = rest[-1]
         if self._trace is not None:
             self._trace.flush(f"round={self.stats['rounds']} hits={self.stats['hits']}/{self.stats['requests']}")
             t_req = self._trace.mark()

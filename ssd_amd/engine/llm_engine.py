@@ -207,6 +207,11 @@ class LLMEngine:
             if getattr(runner, "tp_size", 1) > 1:
                 raise ValueError(f"logprobs is not supported with a tensor-parallel target (tp_size = {runner.tp_size}): every rank "
                                  f"holds a shard of the vocabulary")
+        if sampling_params is not None and sampling_params.seed is not None:
+            # a seeded request draws from its own stream inside the sampling and verify launches (csrc/seeded.hip), draft included
+            for runner in (getattr(self, "model_runner", None), self.draft_runner):
+                if runner is not None and not getattr(runner, "supports_seed", False):
+                    raise ValueError(f"seed is not supported by {type(runner).__name__}: this runner has no per-request random stream")
         self.scheduler.add(Sequence(prompt, sampling_params))
 
     def step(self, step: InferenceStep):

@@ -24,6 +24,7 @@ from ssd_amd.hip import ops as H
 from ssd_amd.hip import filter_ops as HF
 from ssd_amd.hip import penalty_ops as HP
 from ssd_amd.hip import logprob_ops as HL
+from ssd_amd.hip import seed_ops as HS
 from ssd_amd.hip.lib import load_library
 from ssd_amd.model import HipDecoder, AttnMeta
 from ssd_amd.model_config import ModelConfig
@@ -38,17 +39,19 @@ class Sampling(NamedTuple):
     filt: bool = False      # some sampled sequence has top_k / top_p / min_p: truncate the rows first
     pen: bool = False       # some sequence has a penalty or a logit bias: adjust the raw rows in front of everything else
     lp: bool = False        # some sequence asked for log-probabilities (the target only): read the raw rows first, pick after the token
+    seed: bool = False      # some sequence of a sampling batch has a seed: draw with the per-request stream (csrc/seeded.hip)
 
     @property
     def suffix(self) -> str:
         """What a graph's name carries behind "decode" / "decode_chain" / "verify" / "tree"."""
-        return ("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "") + ("_l" if self.lp else "")
+        return (("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "") + ("_l" if self.lp else "")
+                + ("_d" if self.seed else ""))
 
     @classmethod
-    def explicit(cls, temps, filters) -> "Sampling":
+    def explicit(cls, temps, filters, seeds=None) -> "Sampling":
         """The draft server's requests carry arrays, not sequences, and are not penalised."""
         sample = temps is not None and any(t > 0 for t in temps)
-        return cls(sample, sample and filters is not None)
+        return cls(sample, sample and filters is not None, seed=sample and seeds is not None and any(s >= 0 for s in seeds))
 
 
 GREEDY = Sampling()
@@ -60,6 +63,7 @@ class ModelRunner:
     supports_logit_filters = True   # top_k / top_p / min_p (csrc/filter.hip); LLMEngine.add_request refuses them on runners without it
     supports_logit_penalties = True # repetition / presence / frequency penalty, logit_bias (csrc/penalty.hip); refused likewise
     supports_logprobs = True        # SamplingParams(logprobs=N): raw log-probabilities of the target's rows (csrc/logprob.hip); likewise
+    supports_seed = True            # SamplingParams(seed=S): the request's own random stream (csrc/seeded.hip); likewise
     PENALTY_MAX_BIAS = 1024         # logit_bias entries one request may carry: the history table holds max_model_len + this many ids
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
@@ -409,9 +413,12 @@ class ModelRunner:
             self._penalize(lg, n, rows_per_seq, form)
         return lg
 
-    def _draw(self, lg: torch.Tensor, n: int, how: Sampling, rows_per_param: int, salt: int, keep=None, boost: bool = False) -> None:
+    def _draw(self, lg: torch.Tensor, n: int, how: Sampling, rows_per_param: int, salt: int, keep=None, boost: bool = False,
+              pos=None) -> None:
         """Temperature > 0: truncate, keep the rows for the ratio test (keep = (logits_q table, step): what is stored, the boost rows
-        and the draw all see the truncated row), draw d_next with the Gumbel-max sampler, move the RNG on."""
+        and the draw all see the truncated row), draw d_next with the Gumbel-max sampler, move the RNG on.  pos: the positions of
+        the rows' input tokens (the body's position array), which key the stream of a seeded sequence; this is the one place where
+        the purpose of a token draw is chosen -- a draft's tokens are DRAFT, the target's TARGET."""
         V = self.cfg.vocab_size
         if how.filt:
             self._filter(lg, n, rows_per_param)
@@ -423,8 +430,12 @@ class ModelRunner:
             # tokens come from the rescaled distribution, the q that verify() divides by
             H.topk_rows(lg, V, n, V, self.sx_k, self.d_boost)
             kw = dict(boost_idx=self.d_boost, boost_k=self.sx_k, boost_x=self.sx)
-        H.sample_rows(lg, V, n, V, self.d_temps, rows_per_param, self.d_rng, salt, self.d_next, **kw)
-        H.rng_advance(self.d_rng)
+        if how.seed:
+            HS.sample_rows_seeded(lg, V, n, V, self.d_temps, rows_per_param, self.d_rng, salt, self.d_next, self.d_seed, rows_per_param,
+                                  pos, HS.DRAFT if self.is_draft else HS.TARGET, self.d_seed_ws, **kw)
+        else:
+            H.sample_rows(lg, V, n, V, self.d_temps, rows_per_param, self.d_rng, salt, self.d_next, **kw)
+        H.rng_advance(self.d_rng)       # (behind both forms: the unseeded rows of a mixed batch draw from the word)
 
     def _greedy(self, lg, n: int, how: Sampling) -> None:
         """d_next = argmax: over the adjusted rows when they were penalised (the LM head's candidates predate the adjustment)."""
@@ -443,7 +454,8 @@ class ModelRunner:
             self._logprob_rows(B, how, 1)
         lg = self._rows(B, how, 1, "chain" if chain else None)      # a chain step also sees the chain's own tokens so far
         if how.sample:
-            self._draw(lg, B, how, 1, 1, keep=(self.d_logits_q, self.d_step) if chain else None, boost=chain and self.is_draft)
+            self._draw(lg, B, how, 1, 1, keep=(self.d_logits_q, self.d_step) if chain else None, boost=chain and self.is_draft,
+                       pos=self.d_pos)
         elif chain and not how.pen and self.model.has_argmax_parts(B):
             # argmax from the LM head's candidates + the chain advance: one launch
             self.model.argmax_advance(B, self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
@@ -476,9 +488,14 @@ class ModelRunner:
                 H.topk_rows(logits_q, V, B * K, V, self.sx_k, self.d_boost)
                 boost = dict(boost_k=self.sx_k, boost_x=self.sx)
             H.row_lse(logits_q, V, B * K, V, self.d_temps_q, K, self.d_lse_q, boost_idx=self.d_boost if boost else None, **boost)
-            H.verify_ratio(lg, V, logits_q, V, V, B, K, self.d_ids, self.d_next, self.d_lse_p, self.d_lse_q, self.d_temps,
-                           self.d_temps_q, self.d_ratio, self.d_rng, 2, self.d_accept, self.d_recovery, self.d_packed,
-                           boost_idx_q=self.d_boost if boost else None, **boost)
+            if how.seed:    # acceptance uniforms and recovery noise of seeded sequences from their own streams, at the inputs' positions
+                HS.verify_ratio_seeded(lg, V, logits_q, V, V, B, K, self.d_ids, self.d_next, self.d_lse_p, self.d_lse_q, self.d_temps,
+                                       self.d_temps_q, self.d_ratio, self.d_rng, 2, self.d_accept, self.d_recovery, self.d_seed,
+                                       self.d_pos, packed=self.d_packed, boost_idx_q=self.d_boost if boost else None, **boost)
+            else:
+                H.verify_ratio(lg, V, logits_q, V, V, B, K, self.d_ids, self.d_next, self.d_lse_p, self.d_lse_q, self.d_temps,
+                               self.d_temps_q, self.d_ratio, self.d_rng, 2, self.d_accept, self.d_recovery, self.d_packed,
+                               boost_idx_q=self.d_boost if boost else None, **boost)
             H.rng_advance(self.d_rng)
         elif greedy_tail and not how.pen and K + 1 <= 16 and self.model.has_argmax_parts(T):
             # LM head -> [argmax from its candidates + accept / reject] : the verify graph's tail is two launches
@@ -635,11 +652,15 @@ class ModelRunner:
         filters = self._seq_filters(seqs) if sample else None
         pen = self._seq_penalties(seqs) and not (prefill and self.is_draft)
         lp = not self.is_draft and any(getattr(s, "logprobs", None) is not None for s in seqs)     # the target's distribution only
-        return Sampling(sample, filters is not None, pen, lp), dict(temps=temps, filters=filters, seqs=seqs)
+        seeds = [-1 if getattr(s, "seed", None) is None else int(s.seed) for s in seqs] if sample else None
+        how = Sampling(sample, filters is not None, pen, lp, seeds is not None and any(x >= 0 for x in seeds))
+        return how, dict(temps=temps, filters=filters, seqs=seqs, seeds=seeds)
 
-    def _stage_sampling(self, how: Sampling, temps=None, filters=None, seqs=None, back: int = 0, temps_q=None, ratio_rows=None) -> None:
-        """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, and the
-        penalty tables of `seqs` (back: see _upload_penalties).  A greedy batch without penalties uploads nothing."""
+    def _stage_sampling(self, how: Sampling, temps=None, filters=None, seqs=None, back: int = 0, temps_q=None, ratio_rows=None,
+                        seeds=None) -> None:
+        """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, the
+        penalty tables of `seqs` (back: see _upload_penalties), and the seeds (-1: none).  A greedy batch without penalties uploads
+        nothing."""
         if how.sample:
             self._ensure_stochastic()
             self._upload(self.d_temps, list(temps), torch.float32)
@@ -650,11 +671,25 @@ class ModelRunner:
             self._upload(self.d_top_k, list(filters[0]), torch.int32)
             self._upload(self.d_top_p, list(filters[1]), torch.float32)
             self._upload(self.d_min_p, list(filters[2]), torch.float32)
+        if how.seed:        # data, not a capture constant: other seeds replay the same graphs
+            self._ensure_seed()
+            self._upload(self.d_seed, [int(x) for x in seeds], torch.int64)
         if how.pen:
             self._upload_penalties(seqs, back)
         if how.lp:          # the N of every sequence; -1 = did not ask: the kernels skip its rows
             self._ensure_logprob(how.pen)
             self._upload(self.d_lp_ntop, [-1 if getattr(s, "logprobs", None) is None else int(s.logprobs) for s in seqs], torch.int32)
+
+    def _ensure_seed(self) -> None:
+        """Device buffers of csrc/seeded.hip (allocated on first use): a seed per sequence, the slice candidates of every row a body can
+        sample, and the prefill's B last positions (d_pos is per token there)."""
+        if hasattr(self, "d_seed"):
+            return
+        rows = max(self.model.max_logit_rows, self.seq_cap)
+        dev = dict(device=self.device)
+        self.d_seed = torch.full((self.seq_cap,), -1, dtype=torch.int64, **dev)
+        self.d_seed_pos = torch.zeros(self.seq_cap, dtype=torch.int64, **dev)
+        self.d_seed_ws = torch.zeros(HS.sample_seeded_ws_bytes(rows, self.cfg.vocab_size) // 8, dtype=torch.int64, **dev)
 
     def _ensure_logprob(self, copy: bool) -> None:
         """Device buffers of csrc/logprob.hip, sized by the model's logit rows, with the pinned mirrors of what the host reads
@@ -790,7 +825,9 @@ class ModelRunner:
             self._logprob_rows(B, how, 1)
         lg = self._rows(B, how)
         if how.sample:
-            self._draw(lg, B, how, 1, 3)
+            if how.seed:    # the token at position len(s): keyed like the decode that would have drawn it
+                self._upload(self.d_seed_pos, [len(s) - 1 for s in seqs], torch.int64)
+            self._draw(lg, B, how, 1, 3, pos=self.d_seed_pos if how.seed else None)
         else:
             self._greedy(lg, B, how)
         if how.lp:
@@ -868,7 +905,7 @@ class ModelRunner:
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
             if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):       # the pointer is baked in the sampling graphs
                 on_off = (False, True)
-                baked = {"verify" + Sampling(True, f, p, l).suffix for f in on_off for p in on_off for l in on_off}
+                baked = {"verify" + Sampling(True, f, p, l, d).suffix for f in on_off for p in on_off for l in on_off for d in on_off}
                 self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in baked}
             self._lq_ptr = logits_q.data_ptr()
 
@@ -959,13 +996,14 @@ class ModelRunner:
         return B, T, max_q
 
     @torch.inference_mode()
-    def draft_jit(self, rec, num_tokens, tables, temps=None, filters=None) -> torch.Tensor:
+    def draft_jit(self, rec, num_tokens, tables, temps=None, filters=None, seeds=None) -> torch.Tensor:
         """K chained single-token decodes from the recovery token at P = n - 1 (no host sync).  With some
         temperature > 0 the tokens are sampled and the K rows of draft logits are kept for `logits_q`; filters
-        (top_k [B], top_p [B], min_p [B]) truncates them first, as the target truncates its p."""
+        (top_k [B], top_p [B], min_p [B]) truncates them first, as the target truncates its p; seeds ([B], -1 = none) keys the
+        draws of seeded sequences by their own streams."""
         B, K = len(rec), self.K
         self._check_chain_host()
-        how = Sampling.explicit(temps, filters)
+        how = Sampling.explicit(temps, filters, seeds)
         self._note_ctx(max(num_tokens) + self._async_lookahead())
 
         def stage():
@@ -976,7 +1014,7 @@ class ModelRunner:
             self._upload(self.d_ctx, list(num_tokens), torch.int32)
             self._upload_tables(tables)
             self.d_step.zero_()
-            self._stage_sampling(how, temps, filters)
+            self._stage_sampling(how, temps, filters, seeds=seeds)
 
         def chain():
             for _ in range(K):
@@ -1055,7 +1093,8 @@ class ModelRunner:
         self.model.forward(self.d_ids, self.d_tree_pos[d], T, meta)
         self.model.compute_logits(T)
         if how.sample:      # one parameter set per sequence = per mq branch rows; keep every branch's logits for logits_q
-            self._draw(self._rows(T, how), T, how, mq, 4, keep=(self.d_tree_logits, self.d_steps_const[d:]), boost=True)
+            self._draw(self._rows(T, how), T, how, mq, 4, keep=(self.d_tree_logits, self.d_steps_const[d:]), boost=True,
+                       pos=self.d_tree_pos[d])
         elif self.model.has_argmax_parts(T):
             # one launch writes the tokens, the next step's input ids and column d of the [T][K] token table
             self.model.argmax(T, self.d_next, self.d_ids, self.d_tree_tokens.view(-1)[d:], self.K)
@@ -1066,16 +1105,16 @@ class ModelRunner:
         self.d_tree_tokens[:T, d].copy_(self.d_next[:T])
 
     @torch.inference_mode()
-    def draft_tree(self, forks: torch.Tensor, num_tokens, tables, jlists, temps=None, filters=None) -> torch.Tensor:
+    def draft_tree(self, forks: torch.Tensor, num_tokens, tables, jlists, temps=None, filters=None, seeds=None) -> torch.Tensor:
         """K tree-decode steps with the structural branch mask; tokens (greedy, or sampled when some temperature is
-        > 0, from rows truncated by `filters` when given) are chained on the device.  Returns tokens [B*MQ, K]; the
-        branches' logits stay in `tree_logits`."""
+        > 0, from rows truncated by `filters` when given, with the streams of `seeds` when given) are chained on the device.
+        Returns tokens [B*MQ, K]; the branches' logits stay in `tree_logits`."""
         self._ensure_tree_buffers()
         B, K, mq = forks.shape[0], self.K, forks.shape[1]      # mq < MQ_LEN: one member's branch slice (draft data-parallelism)
         assert mq <= self.mq
         T = B * mq
         self._note_ctx(max(num_tokens) + self._async_lookahead())
-        how = Sampling.explicit(temps, filters)
+        how = Sampling.explicit(temps, filters, seeds)
         if how.sample and self.d_tree_logits is None:
                 self.d_tree_logits = torch.zeros(self.max_bs * self.mq, K, self.cfg.vocab_size, dtype=torch.bfloat16, device=self.device)
 
@@ -1098,7 +1137,7 @@ class ModelRunner:
             self._upload(self.d_jidx_flat, [v for j in jlists for v in j], torch.int32)     # packed [B][mq]
             self._upload_tables(tables)
             self.d_ids[:T].copy_(forks.reshape(-1))
-            self._stage_sampling(how, temps, filters)
+            self._stage_sampling(how, temps, filters, seeds=seeds)
 
         def all_steps():                 # the K tree steps in ONE hipGraph (each step has its own static metadata rows)
             for d in range(K):

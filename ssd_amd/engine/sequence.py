@@ -61,6 +61,9 @@ class Sequence:
         self.logprobs = sp.logprobs
         self.logprob_records: list[dict] = []
         self.recovery_logprob: dict | None = None
+        # per-request seed (include/ssd_hip_seed.h; None = the engine's stream).  The stream is keyed by absolute positions, so a
+        # preempted sequence's recomputed prefill draws the numbers the position always had
+        self.seed = sp.seed
         # EAGLE-3 (reference sequence.py:23-24,47-51): the target activation that conditions the next recovery token, and
         # the accepted draft tokens + their target activations that the draft re-deposits ("extends") at the next glue
         self.last_target_hidden_state = None

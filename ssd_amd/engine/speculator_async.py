@@ -58,10 +58,11 @@ class AsyncLink:
         if pump is not None and not (eagle_acts is None and getattr(self.tx, "defer_prefill", False)):
             pump()      # (co-located on a GPU: deferred to the first speculation request, engine/llm_engine.py)
 
-    def speculate(self, keys, num_tokens, block_tables, temps, want_logits: bool = False, eagle=None, filters=None):
+    def speculate(self, keys, num_tokens, block_tables, temps, want_logits: bool = False, eagle=None, filters=None, seeds=None):
         """-> (hits, tokens, logits_q or None).  logits_q bf16 [B, K, V] is requested only when some temperature is
         > 0 (FLAG_WANT_LOGITS) and reaches every TP rank: each rank runs the ratio test on its own device.
-        filters: None, or (top_k [B], top_p [B], min_p [B]) when some sequence has a logit filter (FLAG_FILTER)."""
+        filters: None, or (top_k [B], top_p [B], min_p [B]) when some sequence has a logit filter (FLAG_FILTER).
+        seeds: None, or [B] (-1 = none) when some sequence has a seed (FLAG_SEED)."""
         B, K = len(keys), self.K
         resp, lq = None, None
         V = self.config.hf_config.vocab_size
@@ -71,6 +72,9 @@ class AsyncLink:
             if filters is not None:
                 flags |= P.FLAG_FILTER
                 fkw = {"filters": filters}
+            if seeds is not None:
+                flags |= P.FLAG_SEED
+                fkw["seeds"] = seeds
             if eagle is not None:       # (extend_counts [B], extend_ids [B][K], acts [B, K+1, A])
                 payload = P.pack_speculate(keys, num_tokens, block_tables, temps, self.max_blocks, eagle[0], eagle[1], **fkw)
                 flags |= P.FLAG_EAGLE
@@ -148,6 +152,9 @@ class SpeculatorAsync(SpeculatorBase):
         fkw = {}
         if eagle is None and any(getattr(s, "has_filter", False) for s in seqs):
             fkw = {"filters": ([s.top_k for s in seqs], [s.top_p for s in seqs], [s.min_p for s in seqs])}
+        # ... and so do seeds (an EAGLE-3 draft draws nothing)
+        if eagle is None and any(getattr(s, "seed", None) is not None for s in seqs):
+            fkw["seeds"] = [-1 if s.seed is None else s.seed for s in seqs]
         hits, tokens, logits_q = self.link.speculate(keys, nts, tables, temps, want_logits=want, eagle=eagle, **fkw)
         rows = []
         for seq, toks in zip(seqs, tokens):

@@ -4,7 +4,11 @@ before the temperature, repetition / presence / frequency penalties and logit bi
 
 ``logprobs=N`` asks for the log-probability of every generated token (N = 0) and, beside it, for the N most probable tokens of that
 position (N = 1..20).  They are RAW log-probabilities: log_softmax of the target's bf16 logits, taken before penalties, logit bias,
-temperature and truncation (include/ssd_hip_logprob.h) -- whatever the decoding mode, the target's distribution."""
+temperature and truncation (include/ssd_hip_logprob.h) -- whatever the decoding mode, the target's distribution.
+
+``seed=S`` makes a sampled request reproducible: every random number it consumes comes from a stream keyed by (S, absolute token
+position, purpose, vocabulary index) (include/ssd_hip_seed.h) instead of the engine's own, which depends on what was sampled before and
+on the batch slot.  It has no effect at temperature 0."""
 import math
 from dataclasses import dataclass
 
@@ -30,6 +34,7 @@ class SamplingParams:
     frequency_penalty: float = 0.0      # subtracted per occurrence in the output; 0.0 = off
     logit_bias: dict | None = None      # token id -> value in [-100, 100] added to that token's logit; None = off
     logprobs: int | None = None         # None = off; 0 = each generated token's raw log-probability; 1..20 = also the N most probable
+    seed: int | None = None             # None = off (the engine's stream); 0 <= seed < 2**63: the request draws from its own stream
 
     def __post_init__(self):
         if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or self.top_k < 0:
@@ -56,6 +61,8 @@ class SamplingParams:
         if self.logprobs is not None and (isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int)
                                           or not 0 <= self.logprobs <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be None (off) or an integer in [0, {MAX_LOGPROBS}], got {self.logprobs!r}")
+        if self.seed is not None and (isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 2 ** 63):
+            raise ValueError(f"seed must be None (off) or an integer in [0, 2**63), got {self.seed!r}")
 
     @property
     def active_penalties(self) -> list[str]:
