@@ -2,7 +2,8 @@
 
 Public behaviour kept: ``LLM(model, **Config fields)``; ``generate(prompts, sampling_params, use_tqdm=True,
 stream_callback=None) -> (outputs, METRICS)`` with ``outputs[i] = {"text", "token_ids"}``; the METRICS keys.  A request with
-``SamplingParams(logprobs=N)`` also gets ``"logprobs"`` (one record per token) and ``"cumulative_logprob"``.
+``SamplingParams(logprobs=N)`` also gets ``"logprobs"`` (one record per token) and ``"cumulative_logprob"``; one with
+``SamplingParams(stop_token_ids=[...])`` also gets ``"stop_reason"`` (the stop id that ended it, or None).
 
 Process model (differs by design): one process per GPU, SPMD.  Under ``torchrun`` every rank constructs the same
 engine and calls ``generate`` with the same requests; tensor-parallel ranks stay in lock step through the RCCL
@@ -98,6 +99,7 @@ class LLMEngine:
         self.draft_runner = None
         self._capped_ids: set[int] = set()
         self._logprobs_out: dict[int, list] = {}        # seq id -> the records of a finished request that asked (step() fills it)
+        self._stop_out: dict[int, int | None] = {}      # seq id -> stop_reason of a finished request that set stop_token_ids (likewise)
         self.async_link = None
         self.draft_server = None
         if self.topo.role == "draft":               # dedicated draft GPU of async speculation
@@ -212,7 +214,34 @@ class LLMEngine:
             for runner in (getattr(self, "model_runner", None), self.draft_runner):
                 if runner is not None and not getattr(runner, "supports_seed", False):
                     raise ValueError(f"seed is not supported by {type(runner).__name__}: this runner has no per-request random stream")
+        active = sampling_params.active_constraints if sampling_params is not None else []
+        if active:      # min_tokens / allowed_token_ids / bad_words_ids need a runner that bans entries of the raw rows (the HIP runners
+            # do); stop_token_ids is host work and every runner takes it
+            for runner in (getattr(self, "model_runner", None), self.draft_runner):
+                if runner is not None and not getattr(runner, "supports_logit_constraints", False):
+                    raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no token constraints "
+                                     f"(requested: {', '.join(active)})")
+            self._check_constraints(sampling_params)
         self.scheduler.add(Sequence(prompt, sampling_params))
+
+    def _check_constraints(self, sp: SamplingParams) -> None:
+        """The halves of the constraint validation that need the vocabulary size and the EOS, which SamplingParams does not know."""
+        from ssd_amd.sampling_params import MAX_STOP_TOKEN_IDS
+        V, eos = self.config.hf_config.vocab_size, self.config.eos
+        if sp.allowed_token_ids is not None:
+            over = [t for t in sp.allowed_token_ids if t >= V]
+            if over:
+                raise ValueError(f"allowed_token_ids holds {over[0]}, which is not below the vocabulary size {V}")
+        if sp.min_tokens > 0:
+            stops = set(sp.stop_token_ids or ()) | (set() if sp.ignore_eos else {eos})
+            if len(stops) > MAX_STOP_TOKEN_IDS:
+                raise ValueError(f"min_tokens has {len(stops)} ids to hold back (stop_token_ids and the EOS {eos}): at most "
+                                 f"{MAX_STOP_TOKEN_IDS}")
+            if sp.allowed_token_ids is not None:
+                left = set(sp.allowed_token_ids) - {w[0] for w in sp.bad_words_ids or () if len(w) == 1} - stops
+                if not left:
+                    raise ValueError(f"allowed_token_ids leaves nothing to generate before min_tokens: every id that is not a one-token "
+                                     f"entry of bad_words_ids is in stop_token_ids or is the EOS {eos}")
 
     def step(self, step: InferenceStep):
         t = perf_counter()
@@ -222,6 +251,8 @@ class LLMEngine:
             toks = s.completion_token_ids
             if s.logprobs is not None:
                 self._logprobs_out[s.seq_id] = s.completion_logprobs
+            if s.stop_token_ids:
+                self._stop_out[s.seq_id] = None
             if s.first_token_streamed is not None:      # streamed at the prefill, capped before the round that appends it:
                 toks = toks + [s.first_token_streamed]  # the result must carry what the stream already delivered
                 if s.logprobs is not None:              # ... and that token's record
@@ -241,6 +272,8 @@ class LLMEngine:
         for s in seqs:
             if s.is_finished and s.logprobs is not None:
                 self._logprobs_out[s.seq_id] = s.completion_logprobs
+            if s.is_finished and s.stop_token_ids:
+                self._stop_out[s.seq_id] = s.stop_reason
         return capped + [(s.seq_id, s.completion_token_ids) for s in seqs if s.is_finished]
 
     def is_finished(self) -> bool:
@@ -331,6 +364,7 @@ class LLMEngine:
             METRICS[k] = v
         self._capped_ids.clear()            # finish reasons are per generate() call
         self._logprobs_out.clear()
+        self._stop_out.clear()
         if not isinstance(sampling_params, list):
             sampling_params = [sampling_params] * len(prompts)
         for prompt, sp in zip(prompts, sampling_params):
@@ -390,6 +424,8 @@ class LLMEngine:
                 assert len(records) == len(toks), (len(records), len(toks))
                 result[-1]["logprobs"] = records
                 result[-1]["cumulative_logprob"] = float(sum(r["logprob"] for r in records))
+            if seq_id in self._stop_out:            # SamplingParams(stop_token_ids=...): the stop id that ended the request, or None
+                result[-1]["stop_reason"] = self._stop_out[seq_id]
         if not stream_callback and self.config.verbose:
             self.log_metrics()
         # a snapshot, not the module-level dict itself (the reference returns the global: two engines run one after the other in

@@ -23,6 +23,7 @@ import torch.distributed as dist
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import filter_ops as HF
 from ssd_amd.hip import penalty_ops as HP
+from ssd_amd.hip import constrain_ops as HC
 from ssd_amd.hip import logprob_ops as HL
 from ssd_amd.hip import seed_ops as HS
 from ssd_amd.hip.lib import load_library
@@ -40,12 +41,13 @@ class Sampling(NamedTuple):
     pen: bool = False       # some sequence has a penalty or a logit bias: adjust the raw rows in front of everything else
     lp: bool = False        # some sequence asked for log-probabilities (the target only): read the raw rows first, pick after the token
     seed: bool = False      # some sequence of a sampling batch has a seed: draw with the per-request stream (csrc/seeded.hip)
+    con: bool = False       # some sequence has min_tokens, allowed_token_ids or bad_words_ids: ban entries of the raw rows (csrc/constrain.hip)
 
     @property
     def suffix(self) -> str:
         """What a graph's name carries behind "decode" / "decode_chain" / "verify" / "tree"."""
-        return (("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "") + ("_l" if self.lp else "")
-                + ("_d" if self.seed else ""))
+        return (("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "") + ("_c" if self.con else "")
+                + ("_l" if self.lp else "") + ("_d" if self.seed else ""))
 
     @classmethod
     def explicit(cls, temps, filters, seeds=None) -> "Sampling":
@@ -64,6 +66,7 @@ class ModelRunner:
     supports_logit_penalties = True # repetition / presence / frequency penalty, logit_bias (csrc/penalty.hip); refused likewise
     supports_logprobs = True        # SamplingParams(logprobs=N): raw log-probabilities of the target's rows (csrc/logprob.hip); likewise
     supports_seed = True            # SamplingParams(seed=S): the request's own random stream (csrc/seeded.hip); likewise
+    supports_logit_constraints = True   # min_tokens / allowed_token_ids / bad_words_ids (csrc/constrain.hip); likewise
     PENALTY_MAX_BIAS = 1024         # logit_bias entries one request may carry: the history table holds max_model_len + this many ids
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
@@ -404,13 +407,16 @@ class ModelRunner:
     # parameter set (1, K + 1, the tree width), the RNG salt (1 decode and chain, 2 ratio verify, 3 prefill, 4 tree), the penalty
     # form and what is kept of the sampled rows -- and in the fused greedy launches they use when nothing adjusts the rows.
     def _rows(self, n: int, how: Sampling, rows_per_seq: int = 1, form: str | None = None):
-        """The n raw logit rows of the last compute_logits, penalised when asked (on the raw logits, in front of everything else);
-        None on the plain greedy path, which reads the LM head's argmax candidates instead."""
-        if not (how.sample or how.pen):
+        """The n raw logit rows of the last compute_logits, penalised and constrained when asked (on the raw logits, in front of
+        everything else); None on the plain greedy path, which reads the LM head's argmax candidates instead.  The order of the two
+        does not matter: a banned entry is -inf, and -inf stays -inf under finite penalties and biases."""
+        if not (how.sample or how.pen or how.con):
             return None
         lg = self.model.full_logits(n)
         if how.pen:
             self._penalize(lg, n, rows_per_seq, form)
+        if how.con:
+            self._constrain(lg, n, rows_per_seq, form)
         return lg
 
     def _draw(self, lg: torch.Tensor, n: int, how: Sampling, rows_per_param: int, salt: int, keep=None, boost: bool = False,
@@ -438,8 +444,9 @@ class ModelRunner:
         H.rng_advance(self.d_rng)       # (behind both forms: the unseeded rows of a mixed batch draw from the word)
 
     def _greedy(self, lg, n: int, how: Sampling) -> None:
-        """d_next = argmax: over the adjusted rows when they were penalised (the LM head's candidates predate the adjustment)."""
-        if how.pen:
+        """d_next = argmax: over the adjusted rows when they were penalised or constrained (the LM head's candidates predate the
+        adjustment)."""
+        if how.pen or how.con:
             H.argmax_rows(lg, self.cfg.vocab_size, n, self.cfg.vocab_size, self.d_next)
         else:
             self.model.argmax(n, self.d_next)
@@ -456,7 +463,7 @@ class ModelRunner:
         if how.sample:
             self._draw(lg, B, how, 1, 1, keep=(self.d_logits_q, self.d_step) if chain else None, boost=chain and self.is_draft,
                        pos=self.d_pos)
-        elif chain and not how.pen and self.model.has_argmax_parts(B):
+        elif chain and not (how.pen or how.con) and self.model.has_argmax_parts(B):
             # argmax from the LM head's candidates + the chain advance: one launch
             self.model.argmax_advance(B, self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                                       self.block_size, self.d_spec, self.K, self.d_step)
@@ -497,7 +504,7 @@ class ModelRunner:
                                self.d_temps_q, self.d_ratio, self.d_rng, 2, self.d_accept, self.d_recovery, self.d_packed,
                                boost_idx_q=self.d_boost if boost else None, **boost)
             H.rng_advance(self.d_rng)
-        elif greedy_tail and not how.pen and K + 1 <= 16 and self.model.has_argmax_parts(T):
+        elif greedy_tail and not (how.pen or how.con) and K + 1 <= 16 and self.model.has_argmax_parts(T):
             # LM head -> [argmax from its candidates + accept / reject] : the verify graph's tail is two launches
             self.model.argmax_verify(B, K, self.d_ids, self.d_next, self.d_accept, self.d_recovery, self.d_packed)
         elif greedy_tail:
@@ -653,14 +660,15 @@ class ModelRunner:
         pen = self._seq_penalties(seqs) and not (prefill and self.is_draft)
         lp = not self.is_draft and any(getattr(s, "logprobs", None) is not None for s in seqs)     # the target's distribution only
         seeds = [-1 if getattr(s, "seed", None) is None else int(s.seed) for s in seqs] if sample else None
-        how = Sampling(sample, filters is not None, pen, lp, seeds is not None and any(x >= 0 for x in seeds))
+        con = any(getattr(s, "has_constraint", False) for s in seqs) and not (prefill and self.is_draft)
+        how = Sampling(sample, filters is not None, pen, lp, seeds is not None and any(x >= 0 for x in seeds), con)
         return how, dict(temps=temps, filters=filters, seqs=seqs, seeds=seeds)
 
     def _stage_sampling(self, how: Sampling, temps=None, filters=None, seqs=None, back: int = 0, temps_q=None, ratio_rows=None,
                         seeds=None) -> None:
         """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, the
-        penalty tables of `seqs` (back: see _upload_penalties), and the seeds (-1: none).  A greedy batch without penalties uploads
-        nothing."""
+        penalty tables and the constraints of `seqs` (back: see _upload_penalties), and the seeds (-1: none).  A greedy batch without
+        penalties and constraints uploads nothing."""
         if how.sample:
             self._ensure_stochastic()
             self._upload(self.d_temps, list(temps), torch.float32)
@@ -676,6 +684,8 @@ class ModelRunner:
             self._upload(self.d_seed, [int(x) for x in seeds], torch.int64)
         if how.pen:
             self._upload_penalties(seqs, back)
+        if how.con:
+            self._upload_constraints(seqs, back)
         if how.lp:          # the N of every sequence; -1 = did not ask: the kernels skip its rows
             self._ensure_logprob(how.pen)
             self._upload(self.d_lp_ntop, [-1 if getattr(s, "logprobs", None) is None else int(s.logprobs) for s in seqs], torch.int32)
@@ -817,6 +827,78 @@ class ModelRunner:
         HP.penalize_rows(lg, V, rows, V, rows_per_seq, self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.pen_tab_ld, self.d_pen_len,
                          self.d_pen_par[0], self.d_pen_par[1], self.d_pen_par[2], **extra)
 
+    def _ensure_constraint(self) -> None:
+        """Device buffers of csrc/constrain.hip beside the penalty tables, with their pinned staging (allocated on first use)."""
+        if hasattr(self, "d_con_bits"):
+            return
+        assert self.K + 1 <= HC.MAX_EXTRA + 1, "speculate_k exceeds SSD_CONSTRAIN_MAX_EXTRA"
+        B, W = self.seq_cap, HC.mask_words(self.cfg.vocab_size)
+        dev = dict(device=self.device)
+        self.d_con_bits = torch.zeros(B, W, dtype=torch.int32, **dev)                    # allow mask (uint32 words, moved as int32 bits)
+        self.d_con_tok = torch.zeros(B, HC.MAX_WORD_TOKENS, dtype=torch.int32, **dev)    # flattened bad words
+        self.d_con_off = torch.zeros(B, HC.MAX_WORDS + 1, dtype=torch.int32, **dev)
+        self.d_con_stop = torch.zeros(B, HC.MAX_STOP, dtype=torch.int32, **dev)          # stop ids (+ the EOS) held back by min_tokens
+        self.d_con_tail = torch.zeros(B, HC.TAIL_LD, dtype=torch.int32, **dev)           # the last tokens the host knows
+        self.d_con_par = torch.zeros(5, B, dtype=torch.int32, **dev)                     # rows: allow_on, min_left, stop_len, bw_n, tail_len
+        self._con_stage = {}
+        self._con_bits_owner = [None] * B       # the sequence whose mask row b of d_con_bits holds: a request's mask travels once
+
+    def _upload_constraints(self, seqs, back: int = 0) -> None:
+        """Stage every sequence's allow mask, stop list, bad words, tail and counters.  back: lookahead entries at the end of
+        token_ids that the kernel reads from the round's inputs instead (_upload_penalties).  The allow mask (16 KB at a 128 K
+        vocabulary) is a constant of the request: it travels when its sequence takes a batch row it did not have the step before."""
+        self._ensure_constraint()
+        st = self._con_stage.get(self._stage_set)
+        dsts = (self.d_con_bits, self.d_con_tok, self.d_con_off, self.d_con_stop, self.d_con_tail, self.d_con_par)
+        if st is None:
+            pinned = [torch.zeros(d.shape, dtype=d.dtype).pin_memory() for d in dsts]
+            st = self._con_stage[self._stage_set] = (pinned, [t.numpy() for t in pinned])
+        pinned, (bits, tok, off, stop, tail, par) = st
+        B, V, eos = len(seqs), self.cfg.vocab_size, self.config.eos
+        any_words = False
+        for b, s in enumerate(seqs):
+            par[:, b] = 0
+            if not getattr(s, "has_constraint", False):
+                continue
+            upto = len(s.token_ids) - back
+            if s.allowed_token_ids is not None:
+                par[0, b] = 1
+                if self._con_bits_owner[b] != s.seq_id:
+                    self._con_bits_owner[b] = s.seq_id
+                    bits[b] = s.allow_bits(V).view(np.int32)
+                    self.d_con_bits[b].copy_(pinned[0][b], non_blocking=True)
+            if s.min_tokens > 0:
+                stops = s.stop_list(eos)
+                if len(stops) > HC.MAX_STOP:
+                    raise ValueError(f"sequence {s.seq_id} has {len(stops)} stop ids (the EOS included) to hold back under min_tokens: "
+                                     f"at most {HC.MAX_STOP}")
+                stop[b, :len(stops)] = np.clip(stops, -1, 2 ** 31 - 1)
+                par[1, b], par[2, b] = s.min_left(upto), len(stops)
+            if s.bad_words:
+                flat, offs = s.bad_words_flat
+                tok[b, :len(flat)] = np.clip(flat, -1, 2 ** 31 - 1)
+                off[b, :len(offs)] = offs
+                t = s.constraint_tail(HC.TAIL_LD, upto)
+                tail[b, :len(t)] = np.clip(t, -1, 2 ** 31 - 1)
+                par[3, b], par[4, b] = len(s.bad_words), len(t)
+                any_words = True
+        for d, h, on in zip(dsts[1:5], pinned[1:5], (any_words, any_words, True, any_words)):
+            if on:
+                d[:B].copy_(h[:B], non_blocking=True)
+        self.d_con_par.copy_(pinned[5], non_blocking=True)
+
+    def _constrain(self, lg: torch.Tensor, rows: int, rows_per_seq: int, form: str | None) -> None:
+        """Ban entries of `rows` raw logit rows in place with the uploaded constraints; the forms are those of _penalize: "prefix" --
+        row j of a verify also sees inputs 1..j (d_ids), "chain" -- every row also sees the d_step tokens of its draft chain
+        (d_spec).  Rows of sequences without constraints come back untouched."""
+        V, K = self.cfg.vocab_size, self.K
+        extra = dict(extra=self.d_ids, extra_ld=K + 1) if form == "prefix" else \
+            dict(extra=self.d_spec, extra_ld=K + 1, extra_n=self.d_step) if form == "chain" else {}
+        par = self.d_con_par
+        HC.constrain_rows(lg, V, rows, V, rows_per_seq, allow_on=par[0], allow_bits=self.d_con_bits, min_left=par[1],
+                          stop_ids=self.d_con_stop, stop_len=par[2], bw_tok=self.d_con_tok, bw_off=self.d_con_off, bw_n=par[3],
+                          tail=self.d_con_tail, tail_ld=HC.TAIL_LD, tail_len=par[4], **extra)
+
     def _sample_or_argmax(self, seqs, B: int) -> Sampling:
         """The prefill's first token, eagerly behind the (possibly replayed) forward; a penalised sequence's history is the prompt."""
         how, values = self._seq_sampling(seqs, prefill=True)
@@ -905,7 +987,8 @@ class ModelRunner:
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
             if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):       # the pointer is baked in the sampling graphs
                 on_off = (False, True)
-                baked = {"verify" + Sampling(True, f, p, l, d).suffix for f in on_off for p in on_off for l in on_off for d in on_off}
+                baked = {"verify" + Sampling(True, f, p, l, d, c).suffix for f in on_off for p in on_off for l in on_off for d in on_off
+                         for c in on_off}
                 self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in baked}
             self._lq_ptr = logits_q.data_ptr()
 

@@ -161,7 +161,10 @@ class Scheduler:
                 seq.num_cached_tokens = seq.num_prompt_tokens
             else:
                 seq.num_cached_tokens += 1
-            done = (not seq.ignore_eos and tok == self.eos) or seq.num_completion_tokens == seq.max_new_tokens
+            stopped = seq.stops_at(tok, seq.num_tokens - 1, self.eos)       # the EOS or a stop id, and not before min_tokens
+            if stopped and tok in seq.stop_token_ids:
+                seq.stop_reason = tok
+            done = stopped or seq.num_completion_tokens == seq.max_new_tokens
             if done:
                 seq.status = SequenceStatus.FINISHED
                 bm.deallocate(seq)
@@ -171,14 +174,22 @@ class Scheduler:
 
     # ---- speculative post-step (reference scheduler.py:172-327) ----
     def _clip_suffix(self, seq: Sequence, suffix: list[int]) -> tuple[list[int], bool]:
-        if not seq.ignore_eos and self.eos in suffix:
-            suffix = suffix[:suffix.index(self.eos) + 1]
+        # the first EOS or stop id that counts (Sequence.stops_at: not in front of min_tokens) ends the suffix; it stays in it
+        if seq.stop_token_ids or seq.min_tokens:
+            stop = next((i for i, t in enumerate(suffix) if seq.stops_at(t, seq.num_tokens + i, self.eos)), None)
+        else:                                   # the EOS alone, as ever
+            stop = suffix.index(self.eos) if (not seq.ignore_eos and self.eos in suffix) else None
+        if stop is not None:
+            suffix = suffix[:stop + 1]
         if seq.num_completion_tokens + len(suffix) >= seq.max_new_tokens:
             suffix = suffix[:seq.max_new_tokens - seq.num_completion_tokens]
         if seq.num_tokens + len(suffix) > self.max_model_len:
             suffix = suffix[:max(0, self.max_model_len - seq.num_tokens)]
         n = len(suffix)
-        finished = ((not seq.ignore_eos and self.eos in suffix)
+        stopped = stop is not None and stop < n          # (the clips above may have cut it off again)
+        if stopped and suffix[stop] in seq.stop_token_ids:
+            seq.stop_reason = suffix[stop]
+        finished = (stopped
                     or seq.num_completion_tokens + n == seq.max_new_tokens
                     or seq.num_tokens + n >= self.max_model_len)
         return suffix, finished

@@ -8,6 +8,8 @@ from __future__ import annotations
 from enum import Enum, auto
 from itertools import count
 
+import numpy as np
+
 from ssd_amd.sampling_params import SamplingParams
 
 
@@ -64,6 +66,18 @@ class Sequence:
         # per-request seed (include/ssd_hip_seed.h; None = the engine's stream).  The stream is keyed by absolute positions, so a
         # preempted sequence's recomputed prefill draws the numbers the position always had
         self.seed = sp.seed
+        # hard constraints (include/ssd_hip_constrain.h; None / 0 = off) and stop ids.  What the runner uploads is kept here: the stop
+        # list and the flattened bad words for good, the allow bitmask once its width is known (allow_bits); the tail and the output
+        # count are functions of token_ids and are derived, not mirrored, so a rollback or a preemption cannot leave them behind.
+        # "Output" counts from the request's own prompt, like the penalties' history
+        self.stop_token_ids = tuple(dict.fromkeys(int(t) for t in sp.stop_token_ids)) if sp.stop_token_ids else ()
+        self.stop_reason: int | None = None         # the stop id that ended the request (the scheduler writes it)
+        self.min_tokens = sp.min_tokens
+        self.allowed_token_ids = sorted({int(t) for t in sp.allowed_token_ids}) if sp.allowed_token_ids is not None else None
+        self.bad_words = tuple(dict.fromkeys(tuple(int(t) for t in w) for w in sp.bad_words_ids)) if sp.bad_words_ids else ()
+        self.bad_words_flat = ([t for w in self.bad_words for t in w],
+                               [sum(len(w) for w in self.bad_words[:i]) for i in range(len(self.bad_words) + 1)])
+        self._allow_bits = None
         # EAGLE-3 (reference sequence.py:23-24,47-51): the target activation that conditions the next recovery token, and
         # the accepted draft tokens + their target activations that the draft re-deposits ("extends") at the next glue
         self.last_target_hidden_state = None
@@ -85,6 +99,45 @@ class Sequence:
     def has_penalty(self) -> bool:
         return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
                 or bool(self.logit_bias))
+
+    @property
+    def has_constraint(self) -> bool:
+        """Something the constraint kernel enforces is on (stop_token_ids alone is host work)."""
+        return self.min_tokens > 0 or self.allowed_token_ids is not None or bool(self.bad_words)
+
+    def allow_bits(self, V: int) -> np.ndarray:
+        """uint32 [ceil(V / 32)]: bit t & 31 of word t >> 5 is set for every allowed id below V.  Built once per request."""
+        assert self.allowed_token_ids is not None
+        if self._allow_bits is None or self._allow_bits[0] != V:
+            ids = np.array([t for t in self.allowed_token_ids if t < V], dtype=np.int64)
+            bits = np.zeros((V + 31) // 32, dtype=np.uint32)
+            np.bitwise_or.at(bits, ids >> 5, np.left_shift(np.uint32(1), (ids & 31).astype(np.uint32)))
+            self._allow_bits = (V, bits)
+        return self._allow_bits[1]
+
+    def stop_list(self, eos: int) -> list[int]:
+        """What min_tokens keeps from being generated: the stop ids and, unless the sequence ignores it, the EOS."""
+        return list(dict.fromkeys(list(self.stop_token_ids) + ([] if self.ignore_eos else [int(eos)])))
+
+    def num_output_tokens(self, upto: int | None = None) -> int:
+        """Tokens of token_ids[:upto] behind the request's own prompt."""
+        return max(0, (len(self.token_ids) if upto is None else upto) - self.num_request_prompt_tokens)
+
+    def min_left(self, upto: int | None = None) -> int:
+        """Output tokens still missing to min_tokens in front of the row that predicts token_ids[upto]."""
+        return max(0, self.min_tokens - self.num_output_tokens(upto))
+
+    def constraint_tail(self, n: int, upto: int | None = None) -> list[int]:
+        """The last n tokens of token_ids[:upto]: what a bad word's prefix is matched against."""
+        upto = len(self.token_ids) if upto is None else upto
+        return self.token_ids[max(0, upto - n):upto]
+
+    def stops_at(self, token: int, index: int, eos: int) -> bool:
+        """token, sitting at token_ids[index], ends the request: the EOS (unless ignored) or a stop id, and not before min_tokens
+        output tokens stand in front of it."""
+        if index - self.num_request_prompt_tokens < self.min_tokens:
+            return False
+        return (not self.ignore_eos and token == eos) or token in self.stop_token_ids
 
     def penalty_table(self, upto: int | None = None) -> dict[int, list]:
         """token id -> [occurrences after the request's prompt, occurs in the prompt, bias] over token_ids[:upto] (default: all of

@@ -8,16 +8,34 @@ temperature and truncation (include/ssd_hip_logprob.h) -- whatever the decoding 
 
 ``seed=S`` makes a sampled request reproducible: every random number it consumes comes from a stream keyed by (S, absolute token
 position, purpose, vocabulary index) (include/ssd_hip_seed.h) instead of the engine's own, which depends on what was sampled before and
-on the batch slot.  It has no effect at temperature 0."""
+on the batch slot.  It has no effect at temperature 0.
+
+Hard constraints (include/ssd_hip_constrain.h): ``allowed_token_ids`` restricts generation to a set of ids, ``bad_words_ids`` bans token
+sequences by the Hugging Face NoBadWordsLogitsProcessor rule over prompt + output (a one-token word is always banned; the last token of
+a longer word is banned wherever the tokens in front end with the rest of it), ``min_tokens`` keeps the EOS (unless ``ignore_eos``) and
+every stop id from being generated while the request has fewer output tokens.  Banned entries become -inf in front of the temperature,
+the truncation and the draw; raw log-probabilities are read in front of that.  ``stop_token_ids`` ends the request when one of them is
+emitted (the token stays in ``token_ids``, as the EOS does; they apply even with ``ignore_eos``, which concerns the EOS only) and adds
+the key ``"stop_reason"`` to the request's output: the stop id that ended it, or None.  Multi-token bad words can leave a position
+without any allowed token (every member of a small ``allowed_token_ids`` set banned at once): that is the caller's error and is not
+guarded.  ``stop`` strings are not offered: they need a tokenizer."""
 import math
 from dataclasses import dataclass
 
 
 MAX_LOGPROBS = 20       # SSD_LOGPROB_MAX_N
+MAX_STOP_TOKEN_IDS = 64         # SSD_CONSTRAIN_MAX_STOP (under min_tokens the EOS counts too: LLMEngine.add_request knows it)
+MAX_BAD_WORDS = 128             # SSD_CONSTRAIN_MAX_WORDS
+MAX_BAD_WORD_TOKENS = 1024      # SSD_CONSTRAIN_MAX_WORD_TOKENS
+MAX_BAD_WORD_LEN = 16           # SSD_CONSTRAIN_MAX_WORD_LEN
 
 
 def _is_real(v) -> bool:
     return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def _is_id(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool) and v >= 0
 
 
 @dataclass
@@ -35,6 +53,10 @@ class SamplingParams:
     logit_bias: dict | None = None      # token id -> value in [-100, 100] added to that token's logit; None = off
     logprobs: int | None = None         # None = off; 0 = each generated token's raw log-probability; 1..20 = also the N most probable
     seed: int | None = None             # None = off (the engine's stream); 0 <= seed < 2**63: the request draws from its own stream
+    stop_token_ids: list | None = None      # generation ends when one of these ids is emitted (it stays in token_ids); None = off
+    min_tokens: int = 0                     # the EOS and the stop ids cannot be generated before this many output tokens; 0 = off
+    allowed_token_ids: list | None = None   # only these ids may be generated; None = off
+    bad_words_ids: list | None = None       # token sequences that must not appear (Hugging Face NoBadWordsLogitsProcessor); None = off
 
     def __post_init__(self):
         if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or self.top_k < 0:
@@ -63,12 +85,50 @@ class SamplingParams:
             raise ValueError(f"logprobs must be None (off) or an integer in [0, {MAX_LOGPROBS}], got {self.logprobs!r}")
         if self.seed is not None and (isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 2 ** 63):
             raise ValueError(f"seed must be None (off) or an integer in [0, 2**63), got {self.seed!r}")
+        if self.stop_token_ids is not None:
+            if not isinstance(self.stop_token_ids, (list, tuple)) or not all(_is_id(t) for t in self.stop_token_ids):
+                raise ValueError(f"stop_token_ids must be a list of integers >= 0 or None, got {self.stop_token_ids!r}")
+            if len(set(self.stop_token_ids)) > MAX_STOP_TOKEN_IDS:
+                raise ValueError(f"stop_token_ids holds {len(set(self.stop_token_ids))} distinct ids: at most {MAX_STOP_TOKEN_IDS}")
+        if isinstance(self.min_tokens, bool) or not isinstance(self.min_tokens, int) or self.min_tokens < 0:
+            raise ValueError(f"min_tokens must be an integer >= 0 (0 = off), got {self.min_tokens!r}")
+        if self.min_tokens > self.max_new_tokens:
+            raise ValueError(f"min_tokens = {self.min_tokens} exceeds max_new_tokens = {self.max_new_tokens}")
+        if self.allowed_token_ids is not None:
+            if (not isinstance(self.allowed_token_ids, (list, tuple)) or not self.allowed_token_ids
+                    or not all(_is_id(t) for t in self.allowed_token_ids)):
+                raise ValueError(f"allowed_token_ids must be a non-empty list of integers >= 0 or None, got {self.allowed_token_ids!r}")
+        if self.bad_words_ids is not None:
+            if not isinstance(self.bad_words_ids, (list, tuple)) or not all(
+                    isinstance(w, (list, tuple)) and w and all(_is_id(t) for t in w) for w in self.bad_words_ids):
+                raise ValueError(f"bad_words_ids must be a list of non-empty lists of integers >= 0 or None, got {self.bad_words_ids!r}")
+            if len(self.bad_words_ids) > MAX_BAD_WORDS:
+                raise ValueError(f"bad_words_ids holds {len(self.bad_words_ids)} words: at most {MAX_BAD_WORDS}")
+            longest = max((len(w) for w in self.bad_words_ids), default=0)
+            if longest > MAX_BAD_WORD_LEN:
+                raise ValueError(f"bad_words_ids holds a word of {longest} tokens: at most {MAX_BAD_WORD_LEN}")
+            total = sum(len(w) for w in self.bad_words_ids)
+            if total > MAX_BAD_WORD_TOKENS:
+                raise ValueError(f"bad_words_ids holds {total} tokens in all: at most {MAX_BAD_WORD_TOKENS}")
+        if self.allowed_token_ids is not None:      # what is empty whatever the context; the EOS half is LLMEngine.add_request's
+            left = set(self.allowed_token_ids) - {w[0] for w in self.bad_words_ids or () if len(w) == 1}
+            if not left:
+                raise ValueError("allowed_token_ids leaves nothing to generate: every id is also a one-token entry of bad_words_ids")
+            if self.min_tokens > 0 and not left - set(self.stop_token_ids or ()):
+                raise ValueError("allowed_token_ids leaves nothing to generate before min_tokens: every id that is not a one-token "
+                                 "entry of bad_words_ids is in stop_token_ids")
 
     @property
     def active_penalties(self) -> list[str]:
         """Names of the penalty parameters that are switched on."""
         return [n for n, on in (("repetition_penalty", self.repetition_penalty != 1.0), ("presence_penalty", self.presence_penalty != 0.0),
                                 ("frequency_penalty", self.frequency_penalty != 0.0), ("logit_bias", bool(self.logit_bias))) if on]
+
+    @property
+    def active_constraints(self) -> list[str]:
+        """Names of the parameters that need the constraint kernel (stop_token_ids alone is host work and is not among them)."""
+        return [n for n, on in (("min_tokens", self.min_tokens > 0), ("allowed_token_ids", self.allowed_token_ids is not None),
+                                ("bad_words_ids", bool(self.bad_words_ids))) if on]
 
     @property
     def active_filters(self) -> list[str]:
