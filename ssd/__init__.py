@@ -1,5 +1,6 @@
 """Drop-in alias: ``from ssd import LLM, SamplingParams`` (reference ssd/__init__.py:1-2)."""
 from ssd_amd.sampling_params import SamplingParams  # noqa: F401
+from ssd_amd.guide import TokenAutomaton  # noqa: F401
 
 
 def __getattr__(name):

@@ -222,7 +222,35 @@ class LLMEngine:
                     raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no token constraints "
                                      f"(requested: {', '.join(active)})")
             self._check_constraints(sampling_params)
-        self.scheduler.add(Sequence(prompt, sampling_params))
+        guide = None
+        guided = sampling_params.active_guides if sampling_params is not None else []
+        if guided:      # guided_automaton / guided_choice_ids need a runner that walks the automaton on the device (the HIP runners do)
+            for runner in (getattr(self, "model_runner", None), self.draft_runner):
+                if runner is not None and not getattr(runner, "supports_guided_decoding", False):
+                    raise ValueError(f"{guided[0]} is not supported by {type(runner).__name__}: this runner has no guided decoding")
+            guide = self._check_guide(sampling_params)
+        self.scheduler.add(Sequence(prompt, sampling_params, guide=guide))
+
+    def _check_guide(self, sp: SamplingParams):
+        """The halves of the guide validation that need the vocabulary size and the EOS; returns the automaton the request follows
+        (guided_choice_ids is compiled here, with the engine's EOS)."""
+        from ssd_amd.guide import TokenAutomaton
+        V, eos = self.config.hf_config.vocab_size, self.config.eos
+        if sp.guided_automaton is not None and sp.guided_choice_ids is not None:        # (a dataclass can be changed after its checks)
+            raise ValueError("guided_automaton and guided_choice_ids cannot both be given: a request follows one guide")
+        if sp.guided_choice_ids is not None:
+            if sp.ignore_eos:
+                raise ValueError("guided_choice_ids cannot go with ignore_eos=True: a choice ends on the EOS, so it could never end")
+            if not 0 <= eos < V:
+                raise ValueError(f"guided_choice_ids needs the engine's EOS to end a choice, and this engine has none (eos = {eos})")
+            over = [t for c in sp.guided_choice_ids for t in c if t >= V]
+            if over:
+                raise ValueError(f"guided_choice_ids holds {over[0]}, which is not below the vocabulary size {V}")
+            return TokenAutomaton.from_choices(sp.guided_choice_ids, eos, _what="guided_choice_ids")
+        if sp.guided_automaton.max_token >= V:
+            raise ValueError(f"guided_automaton has an edge on token {sp.guided_automaton.max_token}, which is not below the vocabulary "
+                             f"size {V}")
+        return sp.guided_automaton
 
     def _check_constraints(self, sp: SamplingParams) -> None:
         """The halves of the constraint validation that need the vocabulary size and the EOS, which SamplingParams does not know."""

@@ -24,6 +24,7 @@ from ssd_amd.hip import ops as H
 from ssd_amd.hip import filter_ops as HF
 from ssd_amd.hip import penalty_ops as HP
 from ssd_amd.hip import constrain_ops as HC
+from ssd_amd.hip import guide_ops as HG
 from ssd_amd.hip import logprob_ops as HL
 from ssd_amd.hip import seed_ops as HS
 from ssd_amd.hip.lib import load_library
@@ -42,12 +43,13 @@ class Sampling(NamedTuple):
     lp: bool = False        # some sequence asked for log-probabilities (the target only): read the raw rows first, pick after the token
     seed: bool = False      # some sequence of a sampling batch has a seed: draw with the per-request stream (csrc/seeded.hip)
     con: bool = False       # some sequence has min_tokens, allowed_token_ids or bad_words_ids: ban entries of the raw rows (csrc/constrain.hip)
+    gd: bool = False        # some sequence follows a token automaton: walk it through the round's tokens, ban what its state bans (csrc/guide.hip)
 
     @property
     def suffix(self) -> str:
         """What a graph's name carries behind "decode" / "decode_chain" / "verify" / "tree"."""
         return (("_sf" if self.filt else "_s" if self.sample else "") + ("_p" if self.pen else "") + ("_c" if self.con else "")
-                + ("_l" if self.lp else "") + ("_d" if self.seed else ""))
+                + ("_g" if self.gd else "") + ("_l" if self.lp else "") + ("_d" if self.seed else ""))
 
     @classmethod
     def explicit(cls, temps, filters, seeds=None) -> "Sampling":
@@ -67,6 +69,7 @@ class ModelRunner:
     supports_logprobs = True        # SamplingParams(logprobs=N): raw log-probabilities of the target's rows (csrc/logprob.hip); likewise
     supports_seed = True            # SamplingParams(seed=S): the request's own random stream (csrc/seeded.hip); likewise
     supports_logit_constraints = True   # min_tokens / allowed_token_ids / bad_words_ids (csrc/constrain.hip); likewise
+    supports_guided_decoding = True     # guided_automaton / guided_choice_ids (csrc/guide.hip); likewise
     PENALTY_MAX_BIAS = 1024         # logit_bias entries one request may carry: the history table holds max_model_len + this many ids
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
@@ -407,16 +410,18 @@ class ModelRunner:
     # parameter set (1, K + 1, the tree width), the RNG salt (1 decode and chain, 2 ratio verify, 3 prefill, 4 tree), the penalty
     # form and what is kept of the sampled rows -- and in the fused greedy launches they use when nothing adjusts the rows.
     def _rows(self, n: int, how: Sampling, rows_per_seq: int = 1, form: str | None = None):
-        """The n raw logit rows of the last compute_logits, penalised and constrained when asked (on the raw logits, in front of
-        everything else); None on the plain greedy path, which reads the LM head's argmax candidates instead.  The order of the two
-        does not matter: a banned entry is -inf, and -inf stays -inf under finite penalties and biases."""
-        if not (how.sample or how.pen or how.con):
+        """The n raw logit rows of the last compute_logits, penalised, constrained and guided when asked (on the raw logits, in front
+        of everything else); None on the plain greedy path, which reads the LM head's argmax candidates instead.  The order of the
+        three does not matter: a banned entry is -inf, and -inf stays -inf under finite penalties and biases."""
+        if not (how.sample or how.pen or how.con or how.gd):
             return None
         lg = self.model.full_logits(n)
         if how.pen:
             self._penalize(lg, n, rows_per_seq, form)
         if how.con:
             self._constrain(lg, n, rows_per_seq, form)
+        if how.gd:
+            self._guide(lg, n, rows_per_seq, form)
         return lg
 
     def _draw(self, lg: torch.Tensor, n: int, how: Sampling, rows_per_param: int, salt: int, keep=None, boost: bool = False,
@@ -444,9 +449,9 @@ class ModelRunner:
         H.rng_advance(self.d_rng)       # (behind both forms: the unseeded rows of a mixed batch draw from the word)
 
     def _greedy(self, lg, n: int, how: Sampling) -> None:
-        """d_next = argmax: over the adjusted rows when they were penalised or constrained (the LM head's candidates predate the
-        adjustment)."""
-        if how.pen or how.con:
+        """d_next = argmax: over the adjusted rows when they were penalised, constrained or guided (the LM head's candidates predate
+        the adjustment)."""
+        if how.pen or how.con or how.gd:
             H.argmax_rows(lg, self.cfg.vocab_size, n, self.cfg.vocab_size, self.d_next)
         else:
             self.model.argmax(n, self.d_next)
@@ -463,7 +468,7 @@ class ModelRunner:
         if how.sample:
             self._draw(lg, B, how, 1, 1, keep=(self.d_logits_q, self.d_step) if chain else None, boost=chain and self.is_draft,
                        pos=self.d_pos)
-        elif chain and not (how.pen or how.con) and self.model.has_argmax_parts(B):
+        elif chain and not (how.pen or how.con or how.gd) and self.model.has_argmax_parts(B):
             # argmax from the LM head's candidates + the chain advance: one launch
             self.model.argmax_advance(B, self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                                       self.block_size, self.d_spec, self.K, self.d_step)
@@ -504,7 +509,7 @@ class ModelRunner:
                                self.d_temps_q, self.d_ratio, self.d_rng, 2, self.d_accept, self.d_recovery, self.d_packed,
                                boost_idx_q=self.d_boost if boost else None, **boost)
             H.rng_advance(self.d_rng)
-        elif greedy_tail and not (how.pen or how.con) and K + 1 <= 16 and self.model.has_argmax_parts(T):
+        elif greedy_tail and not (how.pen or how.con or how.gd) and K + 1 <= 16 and self.model.has_argmax_parts(T):
             # LM head -> [argmax from its candidates + accept / reject] : the verify graph's tail is two launches
             self.model.argmax_verify(B, K, self.d_ids, self.d_next, self.d_accept, self.d_recovery, self.d_packed)
         elif greedy_tail:
@@ -661,14 +666,15 @@ class ModelRunner:
         lp = not self.is_draft and any(getattr(s, "logprobs", None) is not None for s in seqs)     # the target's distribution only
         seeds = [-1 if getattr(s, "seed", None) is None else int(s.seed) for s in seqs] if sample else None
         con = any(getattr(s, "has_constraint", False) for s in seqs) and not (prefill and self.is_draft)
-        how = Sampling(sample, filters is not None, pen, lp, seeds is not None and any(x >= 0 for x in seeds), con)
+        gd = any(getattr(s, "guide", None) is not None for s in seqs) and not (prefill and self.is_draft)
+        how = Sampling(sample, filters is not None, pen, lp, seeds is not None and any(x >= 0 for x in seeds), con, gd)
         return how, dict(temps=temps, filters=filters, seqs=seqs, seeds=seeds)
 
     def _stage_sampling(self, how: Sampling, temps=None, filters=None, seqs=None, back: int = 0, temps_q=None, ratio_rows=None,
                         seeds=None) -> None:
         """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, the
-        penalty tables and the constraints of `seqs` (back: see _upload_penalties), and the seeds (-1: none).  A greedy batch without
-        penalties and constraints uploads nothing."""
+        penalty tables, the constraints and the guides of `seqs` (back: see _upload_penalties), and the seeds (-1: none).  A greedy
+        batch without penalties, constraints and guides uploads nothing."""
         if how.sample:
             self._ensure_stochastic()
             self._upload(self.d_temps, list(temps), torch.float32)
@@ -686,6 +692,8 @@ class ModelRunner:
             self._upload_penalties(seqs, back)
         if how.con:
             self._upload_constraints(seqs, back)
+        if how.gd:
+            self._upload_guides(seqs, back)
         if how.lp:          # the N of every sequence; -1 = did not ask: the kernels skip its rows
             self._ensure_logprob(how.pen)
             self._upload(self.d_lp_ntop, [-1 if getattr(s, "logprobs", None) is None else int(s.logprobs) for s in seqs], torch.int32)
@@ -899,13 +907,81 @@ class ModelRunner:
                           stop_ids=self.d_con_stop, stop_len=par[2], bw_tok=self.d_con_tok, bw_off=self.d_con_off, bw_n=par[3],
                           tail=self.d_con_tail, tail_ld=HC.TAIL_LD, tail_len=par[4], **extra)
 
+    def _ensure_guide(self) -> None:
+        """Device tables of csrc/guide.hip: one automaton slot per batch row at the strides of the largest automaton a request may
+        carry, the per-step values and the state of every logit row (allocated on first use)."""
+        if hasattr(self, "d_gd_off"):
+            return
+        assert self.K + 1 <= HG.MAX_EXTRA + 1, "speculate_k exceeds SSD_GUIDE_MAX_EXTRA"
+        B, S, E = self.seq_cap, HG.MAX_STATES, HG.MAX_EDGES
+        dev = dict(device=self.device)
+        self.d_gd_off = torch.zeros(B, S + 1, dtype=torch.int32, **dev)         # CSR offsets
+        self.d_gd_dflt = torch.full((B, S), -1, dtype=torch.int32, **dev)
+        self.d_gd_tok = torch.zeros(B, E, dtype=torch.int32, **dev)
+        self.d_gd_next = torch.zeros(B, E, dtype=torch.int32, **dev)
+        self.d_gd_par = torch.zeros(3, B, dtype=torch.int32, **dev)             # rows: guide_on, state0, n_states
+        self.d_gd_state = torch.full((max(self.model.max_logit_rows, B),), -1, dtype=torch.int32, **dev)
+        self._gd_stage = {}
+        # the sequence whose automaton each slot holds: an automaton (up to 2 MB) travels when its sequence takes a slot it did not
+        # have the step before.  A decode, chain or verify batch uses the slots of its rows, 0 .. n - 1; the eager prefill of B new
+        # requests uses the LAST B slots (_gd_base), which the running batch leaves free while running + new <= max_num_seqs, so an
+        # arrival does not evict the automaton of the sequence decoding in row 0
+        self._gd_owner = [None] * B
+        self._gd_base = 0
+
+    def _upload_guides(self, seqs, back: int = 0) -> None:
+        """Stage guide_on, the state in front of every sequence's first row (Sequence.guide_state: derived from token_ids; back as in
+        _upload_penalties, the kernel walks the round's own tokens) and n_states, every step; the used part of a sequence's tables
+        only when the slot (_gd_base + its row) changes hands, from the pinned copy the sequence keeps (Sequence.guide_pinned: made
+        once per request; the automaton is immutable, so it is never rewritten under a copy in flight)."""
+        self._ensure_guide()
+        st = self._gd_stage.get(self._stage_set)
+        if st is None:
+            pinned = torch.zeros(self.d_gd_par.shape, dtype=torch.int32).pin_memory()
+            st = self._gd_stage[self._stage_set] = (pinned, pinned.numpy())
+        pinned, par = st
+        for b, s in enumerate(seqs):
+            par[:, b] = 0
+            a = getattr(s, "guide", None)
+            if a is None:
+                continue
+            par[0, b], par[1, b], par[2, b] = 1, s.guide_state(len(s.token_ids) - back), a.num_states
+            slot = self._gd_base + b
+            if self._gd_owner[slot] != s.seq_id:
+                self._gd_owner[slot] = s.seq_id
+                n, m = a.num_states, a.num_edges
+                flat, at = s.guide_pinned(), 0
+                for d, k in ((self.d_gd_off, n + 1), (self.d_gd_dflt, n), (self.d_gd_tok, m), (self.d_gd_next, m)):
+                    if k:
+                        d[slot, :k].copy_(flat[at:at + k], non_blocking=True)
+                    at += k
+        self.d_gd_par.copy_(pinned, non_blocking=True)
+
+    def _guide(self, lg: torch.Tensor, rows: int, rows_per_seq: int, form: str | None) -> None:
+        """Ban in place what the automaton state in front of each of `rows` raw logit rows does not allow: the walk from the uploaded
+        states through the tokens the row sees (the forms and buffers of _penalize and _constrain), then the rows kernel.  Rows of
+        sequences without a guide come back untouched."""
+        V, K = self.cfg.vocab_size, self.K
+        extra = dict(extra=self.d_ids, extra_ld=K + 1) if form == "prefix" else \
+            dict(extra=self.d_spec, extra_ld=K + 1, extra_n=self.d_step) if form == "chain" else {}
+        par, o = self.d_gd_par, self._gd_base          # (the per-step values are indexed by the batch row, the tables by the slot)
+        tables = (par[2], self.d_gd_off[o:], self.d_gd_dflt[o:], self.d_gd_tok[o:], self.d_gd_next[o:], HG.MAX_STATES, HG.MAX_EDGES)
+        HG.guide_walk(self.d_gd_state, rows, rows_per_seq, par[0], par[1], *tables, **extra)
+        HG.guide_rows(lg, V, rows, V, self.d_gd_state, rows_per_seq, *tables)
+
     def _sample_or_argmax(self, seqs, B: int) -> Sampling:
         """The prefill's first token, eagerly behind the (possibly replayed) forward; a penalised sequence's history is the prompt."""
         how, values = self._seq_sampling(seqs, prefill=True)
-        self._stage_sampling(how, **values)
-        if how.lp:
-            self._logprob_rows(B, how, 1)
-        lg = self._rows(B, how)
+        if how.gd:          # eager, so the tables' base may differ from the graphs': the last B slots (_ensure_guide)
+            self._ensure_guide()
+            self._gd_base = self.seq_cap - B
+        try:
+            self._stage_sampling(how, **values)
+            if how.lp:
+                self._logprob_rows(B, how, 1)
+            lg = self._rows(B, how)
+        finally:
+            self._gd_base = 0
         if how.sample:
             if how.seed:    # the token at position len(s): keyed like the decode that would have drawn it
                 self._upload(self.d_seed_pos, [len(s) - 1 for s in seqs], torch.int64)
@@ -987,8 +1063,8 @@ class ModelRunner:
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
             if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):       # the pointer is baked in the sampling graphs
                 on_off = (False, True)
-                baked = {"verify" + Sampling(True, f, p, l, d, c).suffix for f in on_off for p in on_off for l in on_off for d in on_off
-                         for c in on_off}
+                baked = {"verify" + Sampling(True, f, p, l, d, c, g).suffix for f in on_off for p in on_off for l in on_off for d in on_off
+                         for c in on_off for g in on_off}
                 self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in baked}
             self._lq_ptr = logits_q.data_ptr()
 

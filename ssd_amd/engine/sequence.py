@@ -23,7 +23,8 @@ class Sequence:
     counter = count()       # process-global, monotonically increasing seq ids (reference sequence.py:15,28)
     block_size = 256        # set by the engine from Config.kvcache_block_size
 
-    def __init__(self, token_ids: list[int], sampling_params: SamplingParams | None = None):
+    def __init__(self, token_ids: list[int], sampling_params: SamplingParams | None = None, guide=None):
+        """guide: the TokenAutomaton LLMEngine.add_request compiled from guided_choice_ids (it needs the engine's EOS)."""
         sp = sampling_params or SamplingParams()
         self.seq_id = next(Sequence.counter)
         self.status = SequenceStatus.WAITING
@@ -78,6 +79,12 @@ class Sequence:
         self.bad_words_flat = ([t for w in self.bad_words for t in w],
                                [sum(len(w) for w in self.bad_words[:i]) for i in range(len(self.bad_words) + 1)])
         self._allow_bits = None
+        # guided decoding (ssd_amd/guide.py, include/ssd_hip_guide.h; None = off): the automaton, and its state after every output
+        # position walked so far -- _guide_states[i] is the state after i output tokens.  Like the tail above the state is a function
+        # of token_ids: guide_state derives it on demand and restore cuts it back with the tokens
+        self.guide = guide if guide is not None else sp.guided_automaton
+        self._guide_states = [self.guide.start] if self.guide is not None else None
+        self._guide_pinned = None
         # EAGLE-3 (reference sequence.py:23-24,47-51): the target activation that conditions the next recovery token, and
         # the accepted draft tokens + their target activations that the draft re-deposits ("extends") at the next glue
         self.last_target_hidden_state = None
@@ -138,6 +145,30 @@ class Sequence:
         if index - self.num_request_prompt_tokens < self.min_tokens:
             return False
         return (not self.ignore_eos and token == eos) or token in self.stop_token_ids
+
+    def guide_state(self, upto: int | None = None) -> int:
+        """The automaton's state after the output tokens of token_ids[:upto] (counted from the request's own prompt): the state in
+        front of the row that predicts token_ids[upto].  -1: a token was not allowed where it stands, nothing guides from there on.
+        Kept incrementally, one state per output position; only what lies in front of `upto` is ever walked, so the placeholders
+        of a lookahead (negative ids, always behind `upto`) are not."""
+        assert self.guide is not None, "guide_state() of a sequence without a guide"
+        st, ids, P = self._guide_states, self.token_ids, self.num_request_prompt_tokens
+        n = max(0, (len(ids) if upto is None else upto) - P)
+        assert P + n <= len(ids)
+        while len(st) <= n:
+            t = ids[P + len(st) - 1]
+            st.append(self.guide.delta(st[-1], t) if t >= 0 else -1)
+        return st[n]
+
+    def guide_pinned(self):
+        """The automaton's flattened tables -- edge_off, dflt, edge_tok, edge_next, one behind the other -- as one pinned int32 tensor:
+        what the runners upload from when the sequence takes a table slot.  Made once per request and shared by the target and the
+        draft runner."""
+        if self._guide_pinned is None:
+            import torch
+            a = self.guide
+            self._guide_pinned = torch.from_numpy(np.concatenate([a.edge_off, a.dflt, a.edge_tok, a.edge_next])).pin_memory()
+        return self._guide_pinned
 
     def penalty_table(self, upto: int | None = None) -> dict[int, list]:
         """token id -> [occurrences after the request's prompt, occurs in the prompt, bias] over token_ids[:upto] (default: all of
@@ -235,4 +266,6 @@ class Sequence:
         n, self.num_tokens, self.last_token, self.num_draft_cached_tokens, self.num_cached_tokens = snap
         if self._pen is not None and self._pen_n > n:       # the history forgets the lookahead tokens before they go
             self._pen_sync(n)
+        if self._guide_states is not None:                  # ... and so do the guide's states
+            del self._guide_states[max(1, n - self.num_request_prompt_tokens + 1):]
         del self.token_ids[n:]

@@ -18,9 +18,21 @@ the truncation and the draw; raw log-probabilities are read in front of that.  `
 emitted (the token stays in ``token_ids``, as the EOS does; they apply even with ``ignore_eos``, which concerns the EOS only) and adds
 the key ``"stop_reason"`` to the request's output: the stop id that ended it, or None.  Multi-token bad words can leave a position
 without any allowed token (every member of a small ``allowed_token_ids`` set banned at once): that is the caller's error and is not
-guarded.  ``stop`` strings are not offered: they need a tokenizer."""
+guarded.  ``stop`` strings are not offered: they need a tokenizer.
+
+Guided decoding (ssd_amd/guide.py, include/ssd_hip_guide.h): ``guided_automaton`` is a ``TokenAutomaton``, a deterministic automaton
+over token ids; at every position only the tokens its current state allows can be generated, and the state follows the output tokens
+from the automaton's start state.  ``guided_choice_ids`` is the common special case: the output is exactly one of the given token
+sequences followed by the EOS (``LLMEngine.add_request`` builds the trie with ``TokenAutomaton.from_choices`` and the engine's EOS, so
+it cannot go with ``ignore_eos``).  At most one of the two may be given.  The guide bans like the constraints above -- -inf in front of
+the temperature, the truncation, the draw and the argmax, raw log-probabilities read in front of it -- and independently of them; a
+position at which the composition leaves nothing allowed (``min_tokens`` holding the EOS back at the end of a choice, say) is the
+caller's error and is not guarded.  A guided request ends as every request does: on the EOS, a stop id or ``max_new_tokens``.
+Compilers from regular expressions or JSON schemas to an automaton need a tokenizer and are not offered."""
 import math
 from dataclasses import dataclass
+
+from ssd_amd.guide import TokenAutomaton, check_choices
 
 
 MAX_LOGPROBS = 20       # SSD_LOGPROB_MAX_N
@@ -57,6 +69,8 @@ class SamplingParams:
     min_tokens: int = 0                     # the EOS and the stop ids cannot be generated before this many output tokens; 0 = off
     allowed_token_ids: list | None = None   # only these ids may be generated; None = off
     bad_words_ids: list | None = None       # token sequences that must not appear (Hugging Face NoBadWordsLogitsProcessor); None = off
+    guided_automaton: TokenAutomaton | None = None      # only what the automaton's current state allows may be generated; None = off
+    guided_choice_ids: list | None = None   # the output is one of these token sequences, then the EOS; None = off
 
     def __post_init__(self):
         if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or self.top_k < 0:
@@ -117,6 +131,23 @@ class SamplingParams:
             if self.min_tokens > 0 and not left - set(self.stop_token_ids or ()):
                 raise ValueError("allowed_token_ids leaves nothing to generate before min_tokens: every id that is not a one-token "
                                  "entry of bad_words_ids is in stop_token_ids")
+
+        if self.guided_automaton is not None and self.guided_choice_ids is not None:
+            raise ValueError("guided_automaton and guided_choice_ids cannot both be given: a request follows one guide")
+        if self.guided_automaton is not None and not isinstance(self.guided_automaton, TokenAutomaton):
+            raise ValueError(f"guided_automaton must be a TokenAutomaton or None, got {type(self.guided_automaton).__name__}")
+        if self.guided_choice_ids is not None:
+            if self.ignore_eos:
+                raise ValueError("guided_choice_ids cannot go with ignore_eos=True: a choice ends on the EOS, so it could never end")
+            # the shape and the limits, which do not depend on the EOS; LLMEngine.add_request builds the automaton the request follows,
+            # so the trie is built here only where the tokens' count alone does not settle the limits
+            check_choices(self.guided_choice_ids, "guided_choice_ids", trie=False)
+
+    @property
+    def active_guides(self) -> list[str]:
+        """Names of the guided-decoding parameters that are switched on (at most one)."""
+        return [n for n, on in (("guided_automaton", self.guided_automaton is not None),
+                                ("guided_choice_ids", self.guided_choice_ids is not None)) if on]
 
     @property
     def active_penalties(self) -> list[str]:
