@@ -11,16 +11,16 @@
 //   4. every thread builds an 8-bit ban mask for each of its two 8-entry chunks -- from one 4-byte load of the allow word that covers
 //      the chunk and from the compacted list -- and then: nothing banned: the chunk is neither read nor written; all banned: one
 //      16-byte store; otherwise one 16-byte load, the banned halves replaced, one 16-byte store.  A chunk that crosses V or a row that
-//      is not 16-byte aligned takes 2-byte stores of its banned entries instead.
+//      is not 16-byte aligned takes 2-byte stores of its banned entries instead (ban_chunk, rows.h).
 // A chunk belongs to one thread whatever the path, so every entry has exactly one writer: a sparse ban is never a separate store that
 // could race a neighbour's read-modify-write.  The same input gives the same bits on every run.
 #include "common.h"
+#include "rows.h"
 
 constexpr int CN_THREADS = 256;
 constexpr int CN_PER = 2;                                               // 8-entry chunks per thread
 constexpr int CN_SLOTS = SSD_CONSTRAIN_MAX_STOP + SSD_CONSTRAIN_MAX_WORDS;
 constexpr int CN_CTX = SSD_CONSTRAIN_MAX_WORD_LEN - 1 + SSD_CONSTRAIN_MAX_EXTRA;
-constexpr uint32_t CN_NINF = 0xff80u;
 static_assert(SSD_CONSTRAIN_SLICE == CN_THREADS * CN_PER * 8, "one slice = two chunks per thread");
 static_assert(CN_SLOTS % 64 == 0 && CN_SLOTS <= CN_THREADS, "one thread per slot, whole waves in the compaction");
 static_assert(SSD_CONSTRAIN_MAX_WORD_LEN - 1 <= 64 && SSD_CONSTRAIN_MAX_EXTRA + 64 <= CN_THREADS, "one thread per context token");
@@ -37,7 +37,7 @@ constrain_rows_kernel(bf16_t* __restrict__ logits, long ld, int V, int rows_per_
   __shared__ int nhit;
   const int row = blockIdx.y, sl = blockIdx.x, tid = threadIdx.x;
   const int b = row / rows_per_seq;
-  const int e = extra ? (extra_n ? min(max(*extra_n, 0), extra_ld - 1) : row - b * rows_per_seq) : 0;
+  const int e = rows_seen(extra, extra_ld, extra_n, row, b, rows_per_seq);
   const bool on = allow_on && allow_on[b] != 0;
   const int ns = (stop_ids && e < min_left[b]) ? min(max(stop_len[b], 0), SSD_CONSTRAIN_MAX_STOP) : 0;
   const int nw = bw_tok ? min(max(bw_n[b], 0), SSD_CONSTRAIN_MAX_WORDS) : 0;
@@ -102,28 +102,7 @@ constrain_rows_kernel(bf16_t* __restrict__ logits, long ld, int V, int rows_per_
       const int d = hit[i];
       if ((d >> 3) == c) ban |= 1u << (d & 7);
     }
-    if (base + 8 > V) ban &= (1u << (V - base)) - 1u;
-    if (ban == 0) continue;
-    if (vec && base + 8 <= V) {
-      u32x4_t q;
-      if (ban == 0xffu) {
-        q = u32x4_t{CN_NINF | (CN_NINF << 16), CN_NINF | (CN_NINF << 16), CN_NINF | (CN_NINF << 16), CN_NINF | (CN_NINF << 16)};
-      } else {
-        q = *reinterpret_cast<const u32x4_t*>(x + base);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          uint32_t w = q[k];
-          if ((ban >> (2 * k)) & 1u) w = (w & 0xffff0000u) | CN_NINF;
-          if ((ban >> (2 * k + 1)) & 1u) w = (w & 0x0000ffffu) | (CN_NINF << 16);
-          q[k] = w;
-        }
-      }
-      *reinterpret_cast<u32x4_t*>(x + base) = q;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if ((ban >> k) & 1u) x[base + k] = (bf16_t)CN_NINF;
-    }
+    ban_chunk(x, base, V, vec, ban);
   }
 }
 

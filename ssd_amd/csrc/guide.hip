@@ -11,15 +11,15 @@
 // The rows kernel builds the slice's 4096-bit allow bitmap in LDS: all ones under a default, all zeros without; the state's edges
 // inside the slice (two lower bounds) then set their bit (next != -1) or clear it (next == -1) with LDS atomics.  OR and AND-NOT
 // commute and a token has one edge at most, so the bits do not depend on the order.  Each thread then bans ~allow of its chunks with
-// the write rules of constrain.hip: nothing banned -- neither read nor written; all banned -- one 16-byte store; otherwise 16-byte
+// the write rules of constrain.hip (ban_chunk, rows.h): nothing banned -- neither read nor written; all banned -- one 16-byte store; otherwise 16-byte
 // load, banned halves replaced, 16-byte store; a chunk that crosses V or an unaligned row -- 2-byte stores.  One writer per entry.
 #include "common.h"
+#include "rows.h"
 
 constexpr int GD_THREADS = 256;
 constexpr int GD_PER = 2;                                               // 8-entry chunks per thread
 constexpr int GD_WORDS = SSD_GUIDE_SLICE / 32;
 constexpr int GD_ROUNDS = 2;                                            // narrowing rounds of the search: 64^(GD_ROUNDS + 1) edges
-constexpr uint32_t GD_NINF = 0xff80u;
 static_assert(SSD_GUIDE_SLICE == GD_THREADS * GD_PER * 8, "one slice = two chunks per thread");
 static_assert(GD_WORDS <= GD_THREADS, "one thread per bitmap word");
 static_assert(SSD_GUIDE_MAX_EDGES == 64 * 64 * 64, "two narrowing rounds and a compare per lane");
@@ -75,7 +75,7 @@ guide_walk_kernel(int32_t* __restrict__ state_rows, int T, int rows_per_seq, con
   if (guide_on[b] == 0 || s < 0 || s >= ns) s = -1;
   const bool prefix = extra && !extra_n;
   // steps the last row sees; the prefix form writes a row in front of every step (rows <= rows_per_seq <= extra_ld there)
-  const int steps = !extra ? 0 : prefix ? rows - 1 : min(max(*extra_n, 0), extra_ld - 1);
+  const int steps = prefix ? rows - 1 : rows_seen(extra, extra_ld, extra_n, r0, b, rows_per_seq);
   const int32_t* tok = edge_tok + (size_t)b * edges_ld;
   const int32_t* nxt = edge_next + (size_t)b * edges_ld;
   for (int k = 0; k < steps; ++k) {           // (bounded by extra_ld - 1 <= SSD_GUIDE_MAX_EXTRA)
@@ -139,28 +139,7 @@ guide_rows_kernel(bf16_t* __restrict__ logits, long ld, int V, const int32_t* __
     const int base = lo + c * 8;
     if (base >= V) continue;
     uint32_t ban = ~(allow[c >> 2] >> ((c & 3) * 8)) & 0xffu;
-    if (base + 8 > V) ban &= (1u << (V - base)) - 1u;
-    if (ban == 0) continue;
-    if (vec && base + 8 <= V) {
-      u32x4_t q;
-      if (ban == 0xffu) {
-        q = u32x4_t{GD_NINF | (GD_NINF << 16), GD_NINF | (GD_NINF << 16), GD_NINF | (GD_NINF << 16), GD_NINF | (GD_NINF << 16)};
-      } else {
-        q = *reinterpret_cast<const u32x4_t*>(x + base);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          uint32_t w = q[k];
-          if ((ban >> (2 * k)) & 1u) w = (w & 0xffff0000u) | GD_NINF;
-          if ((ban >> (2 * k + 1)) & 1u) w = (w & 0x0000ffffu) | (GD_NINF << 16);
-          q[k] = w;
-        }
-      }
-      *reinterpret_cast<u32x4_t*>(x + base) = q;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if ((ban >> k) & 1u) x[base + k] = (bf16_t)GD_NINF;
-    }
+    ban_chunk(x, base, V, vec, ban);
   }
 }
 

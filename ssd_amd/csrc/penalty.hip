@@ -13,6 +13,7 @@
 // the same bits on every run.  Every fp32 operation is an explicit round-to-nearest intrinsic: nothing is contracted into an FMA and
 // the division is the IEEE one, whatever the compiler flags.
 #include "common.h"
+#include "rows.h"
 
 constexpr int PN_THREADS = 256;
 
@@ -41,8 +42,7 @@ penalize_rows_kernel(bf16_t* __restrict__ logits, long ld, int V, int rows_per_s
   const float r = rep[b], p = pres[b], f = freq[b];
   const bool pen = !(r == 1.f && p == 0.f && f == 0.f);
   const int n = tab_ids ? min(max(tab_len[b], 0), tab_ld) : 0;
-  int m = 0;                    // extra tokens this row sees: they only matter to r, p and f
-  if (extra && pen) m = extra_n ? min(max(*extra_n, 0), extra_ld - 1) : row - b * rows_per_seq;
+  const int m = pen ? rows_seen(extra, extra_ld, extra_n, row, b, rows_per_seq) : 0;     // they only matter to r, p and f
   if (n == 0 && m == 0) return;
   bf16_t* x = logits + (size_t)row * ld;
 

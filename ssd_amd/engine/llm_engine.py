@@ -184,52 +184,43 @@ class LLMEngine:
             if self.tokenizer is None:
                 raise ValueError("string prompts need a tokenizer in the model directory; pass token-id lists")
             prompt = self.tokenizer.encode(prompt)
-        active = sampling_params.active_filters if sampling_params is not None else []
-        if active:      # top_k / top_p / min_p need a runner that truncates the sampled rows (the HIP runners do)
-            for runner in (getattr(self, "model_runner", None), self.draft_runner):
-                if runner is not None and not getattr(runner, "supports_logit_filters", False):
-                    raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no logit filter "
-                                     f"(requested: {', '.join(active)})")
-        active = sampling_params.active_penalties if sampling_params is not None else []
-        if active:      # penalties and logit_bias need a runner that adjusts the raw rows from the token history (the HIP runners do)
-            for runner in (getattr(self, "model_runner", None), self.draft_runner):
-                if runner is not None and not getattr(runner, "supports_logit_penalties", False):
-                    raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no logit penalties "
-                                     f"(requested: {', '.join(active)})")
-                cap = getattr(runner, "PENALTY_MAX_BIAS", None)
-                if cap is not None and sampling_params.logit_bias and len(sampling_params.logit_bias) > cap:
-                    raise ValueError(f"logit_bias has {len(sampling_params.logit_bias)} entries: the history table of "
-                                     f"{type(runner).__name__} holds at most {cap} biased ids beside the sequence's own tokens")
-        if sampling_params is not None and sampling_params.logprobs is not None:
+        sp = sampling_params
+        both = [r for r in (getattr(self, "model_runner", None), self.draft_runner) if r is not None]
+        # what follows needs runners that have the kernel (the HIP runners do); stop_token_ids is host work and every runner takes it
+        active = sp.active_filters if sp is not None else []
+        self._refuse(both, "supports_logit_filters", active, f"this runner has no logit filter (requested: {', '.join(active)})")
+        active = sp.active_penalties if sp is not None else []
+        self._refuse(both, "supports_logit_penalties", active, f"this runner has no logit penalties (requested: {', '.join(active)})")
+        for runner in both if active else []:
+            cap = getattr(runner, "PENALTY_MAX_BIAS", None)
+            if cap is not None and sp.logit_bias and len(sp.logit_bias) > cap:
+                raise ValueError(f"logit_bias has {len(sp.logit_bias)} entries: the history table of "
+                                 f"{type(runner).__name__} holds at most {cap} biased ids beside the sequence's own tokens")
+        if sp is not None and sp.logprobs is not None:
             # log-probabilities come from the target's raw rows (csrc/logprob.hip): the draft is never asked, so an asynchronous draft
             # on its own GPU is fine; a tensor-parallel target holds a shard of the vocabulary per rank and refuses
             runner = getattr(self, "model_runner", None)
-            if runner is not None and not getattr(runner, "supports_logprobs", False):
-                raise ValueError(f"logprobs is not supported by {type(runner).__name__}: this runner has no log-probability kernel")
+            self._refuse([r for r in both if r is runner], "supports_logprobs", ["logprobs"], "this runner has no log-probability kernel")
             if getattr(runner, "tp_size", 1) > 1:
                 raise ValueError(f"logprobs is not supported with a tensor-parallel target (tp_size = {runner.tp_size}): every rank "
                                  f"holds a shard of the vocabulary")
-        if sampling_params is not None and sampling_params.seed is not None:
-            # a seeded request draws from its own stream inside the sampling and verify launches (csrc/seeded.hip), draft included
-            for runner in (getattr(self, "model_runner", None), self.draft_runner):
-                if runner is not None and not getattr(runner, "supports_seed", False):
-                    raise ValueError(f"seed is not supported by {type(runner).__name__}: this runner has no per-request random stream")
-        active = sampling_params.active_constraints if sampling_params is not None else []
-        if active:      # min_tokens / allowed_token_ids / bad_words_ids need a runner that bans entries of the raw rows (the HIP runners
-            # do); stop_token_ids is host work and every runner takes it
-            for runner in (getattr(self, "model_runner", None), self.draft_runner):
-                if runner is not None and not getattr(runner, "supports_logit_constraints", False):
-                    raise ValueError(f"{active[0]} is not supported by {type(runner).__name__}: this runner has no token constraints "
-                                     f"(requested: {', '.join(active)})")
-            self._check_constraints(sampling_params)
-        guide = None
-        guided = sampling_params.active_guides if sampling_params is not None else []
-        if guided:      # guided_automaton / guided_choice_ids need a runner that walks the automaton on the device (the HIP runners do)
-            for runner in (getattr(self, "model_runner", None), self.draft_runner):
-                if runner is not None and not getattr(runner, "supports_guided_decoding", False):
-                    raise ValueError(f"{guided[0]} is not supported by {type(runner).__name__}: this runner has no guided decoding")
-            guide = self._check_guide(sampling_params)
+        if sp is not None and sp.seed is not None:      # a seeded request draws from its own stream (csrc/seeded.hip), draft included
+            self._refuse(both, "supports_seed", ["seed"], "this runner has no per-request random stream")
+        active = sp.active_constraints if sp is not None else []
+        self._refuse(both, "supports_logit_constraints", active, f"this runner has no token constraints (requested: {', '.join(active)})")
+        if active:
+            self._check_constraints(sp)
+        guided = sp.active_guides if sp is not None else []
+        self._refuse(both, "supports_guided_decoding", guided, "this runner has no guided decoding")
+        guide = self._check_guide(sp) if guided else None
         self.scheduler.add(Sequence(prompt, sampling_params, guide=guide))
+
+    @staticmethod
+    def _refuse(runners, attr: str, fields, phrase: str) -> None:
+        """Raise, naming the first of `fields` (the parameters the request set), if one of `runners` lacks the class attribute `attr`."""
+        for runner in runners if fields else []:
+            if not getattr(runner, attr, False):
+                raise ValueError(f"{fields[0]} is not supported by {type(runner).__name__}: {phrase}")
 
     def _check_guide(self, sp: SamplingParams):
         """The halves of the guide validation that need the vocabulary size and the EOS; returns the automaton the request follows

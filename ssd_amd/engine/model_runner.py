@@ -16,16 +16,11 @@ from __future__ import annotations
 
 from typing import NamedTuple
 
-import numpy as np
 import torch
 import torch.distributed as dist
 
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import filter_ops as HF
-from ssd_amd.hip import penalty_ops as HP
-from ssd_amd.hip import constrain_ops as HC
-from ssd_amd.hip import guide_ops as HG
-from ssd_amd.hip import logprob_ops as HL
 from ssd_amd.hip import seed_ops as HS
 from ssd_amd.hip.lib import load_library
 from ssd_amd.model import HipDecoder, AttnMeta
@@ -33,6 +28,7 @@ from ssd_amd.model_config import ModelConfig
 from ssd_amd import weights as W
 from ssd_amd.utils.graphs import capture
 from ssd_amd.engine.async_proto import to_device
+from ssd_amd.engine.logit_rules import RULES, Logprobs, Penalties, RuleSizes
 
 
 class Sampling(NamedTuple):
@@ -44,6 +40,11 @@ class Sampling(NamedTuple):
     seed: bool = False      # some sequence of a sampling batch has a seed: draw with the per-request stream (csrc/seeded.hip)
     con: bool = False       # some sequence has min_tokens, allowed_token_ids or bad_words_ids: ban entries of the raw rows (csrc/constrain.hip)
     gd: bool = False        # some sequence follows a token automaton: walk it through the round's tokens, ban what its state bans (csrc/guide.hip)
+
+    @property
+    def adjusts(self) -> bool:
+        """Some rule rewrote the raw rows: the LM head's argmax candidates predate that, so the fused greedy launches do not apply."""
+        return self.pen or self.con or self.gd
 
     @property
     def suffix(self) -> str:
@@ -70,7 +71,7 @@ class ModelRunner:
     supports_seed = True            # SamplingParams(seed=S): the request's own random stream (csrc/seeded.hip); likewise
     supports_logit_constraints = True   # min_tokens / allowed_token_ids / bad_words_ids (csrc/constrain.hip); likewise
     supports_guided_decoding = True     # guided_automaton / guided_choice_ids (csrc/guide.hip); likewise
-    PENALTY_MAX_BIAS = 1024         # logit_bias entries one request may carry: the history table holds max_model_len + this many ids
+    PENALTY_MAX_BIAS = Penalties.MAX_BIAS       # logit_bias entries one request may carry
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
                  tp_size: int = 1, tp_group=None, model_path: str | None = None, weights_seed: int = 0,
@@ -179,6 +180,8 @@ class ModelRunner:
         # records of the tokens the last run / verify_chain returned, for the sequences that asked (else None): run -> one record or
         # None per sequence; verify_chain -> per sequence the records of its accepted draft tokens and of the new recovery token
         self.last_logprobs = None
+        self.rules: dict = {}       # Sampling field -> the rule object of engine/logit_rules.py, built by the first batch that needs it
+        self.logprobs = None        # likewise its Logprobs
 
     def _setup_custom_ar(self, want: bool | None) -> None:
         """Enable the one-shot all-reduce for the small TP sums when (a) tensor parallelism is on, (b) it is not
@@ -409,19 +412,37 @@ class ModelRunner:
     # The tail "logits -> (penalise) -> (truncate) -> draw or argmax" of every body, in three pieces.  Bodies differ in the rows per
     # parameter set (1, K + 1, the tree width), the RNG salt (1 decode and chain, 2 ratio verify, 3 prefill, 4 tree), the penalty
     # form and what is kept of the sampled rows -- and in the fused greedy launches they use when nothing adjusts the rows.
-    def _rows(self, n: int, how: Sampling, rows_per_seq: int = 1, form: str | None = None):
-        """The n raw logit rows of the last compute_logits, penalised, constrained and guided when asked (on the raw logits, in front
-        of everything else); None on the plain greedy path, which reads the LM head's argmax candidates instead.  The order of the
-        three does not matter: a banned entry is -inf, and -inf stays -inf under finite penalties and biases."""
-        if not (how.sample or how.pen or how.con or how.gd):
+    def _rule_sizes(self) -> RuleSizes:
+        return RuleSizes(self.seq_cap, self.cfg.vocab_size, self.K, self.config.max_model_len, self.model.max_logit_rows, self.config.eos,
+                         self.device)
+
+    def _rules(self, how: Sampling) -> list:
+        """The rules `how` asks for, in the order they run: penalise, constrain, guide.  (The order does not matter to the result: a
+        banned entry is -inf, and -inf stays -inf under finite penalties and biases.)"""
+        on = [(field, cls) for field, cls in RULES if getattr(how, field)]
+        for field, cls in on:
+            if field not in self.rules:
+                self.rules[field] = cls(self._rule_sizes())
+        return [self.rules[field] for field, _ in on]
+
+    def _extras(self, form: str | None) -> dict:
+        """What a row sees beside its sequence's staged history.  None: nothing; "prefix": row j of a verify also sees inputs 1..j of
+        its K+1 inputs (d_ids); "chain": every row also sees the d_step tokens its draft chain has produced so far (d_spec)."""
+        if form == "prefix":
+            return dict(extra=self.d_ids, extra_ld=self.K + 1)
+        if form == "chain":
+            return dict(extra=self.d_spec, extra_ld=self.K + 1, extra_n=self.d_step)
+        return {}
+
+    def _rows(self, n: int, how: Sampling, rows_per_seq: int = 1, form: str | None = None, base: int = 0):
+        """The n raw logit rows of the last compute_logits, with the rules of `how` applied (on the raw logits, in front of everything
+        else); None on the plain greedy path, which reads the LM head's argmax candidates instead."""
+        if not (how.sample or how.adjusts):
             return None
         lg = self.model.full_logits(n)
-        if how.pen:
-            self._penalize(lg, n, rows_per_seq, form)
-        if how.con:
-            self._constrain(lg, n, rows_per_seq, form)
-        if how.gd:
-            self._guide(lg, n, rows_per_seq, form)
+        extras = self._extras(form)
+        for rule in self._rules(how):
+            rule.apply(lg, n, rows_per_seq, extras, base)
         return lg
 
     def _draw(self, lg: torch.Tensor, n: int, how: Sampling, rows_per_param: int, salt: int, keep=None, boost: bool = False,
@@ -449,9 +470,8 @@ class ModelRunner:
         H.rng_advance(self.d_rng)       # (behind both forms: the unseeded rows of a mixed batch draw from the word)
 
     def _greedy(self, lg, n: int, how: Sampling) -> None:
-        """d_next = argmax: over the adjusted rows when they were penalised, constrained or guided (the LM head's candidates predate
-        the adjustment)."""
-        if how.pen or how.con or how.gd:
+        """d_next = argmax: over the adjusted rows when a rule rewrote them."""
+        if how.adjusts:
             H.argmax_rows(lg, self.cfg.vocab_size, n, self.cfg.vocab_size, self.d_next)
         else:
             self.model.argmax(n, self.d_next)
@@ -463,12 +483,12 @@ class ModelRunner:
         self.model.compute_logits(B)
         if how.lp:          # (the target's decode only: a draft never builds how.lp)
             assert not chain
-            self._logprob_rows(B, how, 1)
+            self.logprobs.rows(self.model.logits, B, 1, how.pen)
         lg = self._rows(B, how, 1, "chain" if chain else None)      # a chain step also sees the chain's own tokens so far
         if how.sample:
             self._draw(lg, B, how, 1, 1, keep=(self.d_logits_q, self.d_step) if chain else None, boost=chain and self.is_draft,
                        pos=self.d_pos)
-        elif chain and not (how.pen or how.con or how.gd) and self.model.has_argmax_parts(B):
+        elif chain and not how.adjusts and self.model.has_argmax_parts(B):
             # argmax from the LM head's candidates + the chain advance: one launch
             self.model.argmax_advance(B, self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                                       self.block_size, self.d_spec, self.K, self.d_step)
@@ -476,7 +496,7 @@ class ModelRunner:
         else:
             self._greedy(lg, B, how)
         if how.lp:
-            self._logprob_pick(B, how)
+            self.logprobs.pick(self.model.logits, B, self.d_next, how.pen)
         if chain:
             H.draft_advance(self.d_next, self.d_ids, self.d_pos, self.d_slots, self.d_ctx, self.d_bt, self.max_blocks,
                             self.block_size, self.d_spec, self.K, self.d_step, B)
@@ -487,7 +507,7 @@ class ModelRunner:
         self.model.forward(self.d_ids, self.d_pos, T, self._meta("verify", B))
         self.model.compute_logits(T)
         if how.lp:
-            self._logprob_rows(T, how, K + 1)
+            self.logprobs.rows(self.model.logits, T, K + 1, how.pen)
         # penalised: row j with the history autoregressive decoding would have had there, the table + inputs 1..j of the round
         lg = self._rows(T, how, K + 1, "prefix")
         if how.sample:      # temperature > 0: ratio acceptance + residual resampling (utils/verify.py:50-167)
@@ -509,15 +529,14 @@ class ModelRunner:
                                self.d_temps_q, self.d_ratio, self.d_rng, 2, self.d_accept, self.d_recovery, self.d_packed,
                                boost_idx_q=self.d_boost if boost else None, **boost)
             H.rng_advance(self.d_rng)
-        elif greedy_tail and not (how.pen or how.con or how.gd) and K + 1 <= 16 and self.model.has_argmax_parts(T):
+        elif greedy_tail and not how.adjusts and K + 1 <= 16 and self.model.has_argmax_parts(T):
             # LM head -> [argmax from its candidates + accept / reject] : the verify graph's tail is two launches
             self.model.argmax_verify(B, K, self.d_ids, self.d_next, self.d_accept, self.d_recovery, self.d_packed)
         elif greedy_tail:
             self._greedy(lg, T, how)
             H.verify_greedy(self.d_next, self.d_ids, B, K, self.d_accept, self.d_recovery, self.d_packed)
         if how.lp:          # accepted inputs and the recovery token of every sequence, from the raw rows
-            HL.logprob_pick_verify(self._logprob_src(how), V, B, K, V, self.d_ids, self.d_accept, self.d_recovery, self.d_lp_lse,
-                                   self.d_lp_ntop, self.d_lp_out)
+            self.logprobs.pick_verify(self.model.logits, B, K, self.d_ids, self.d_accept, self.d_recovery, how.pen)
 
     def _launch(self, key, body) -> None:
         """Replay the captured hipGraph for `key`, capturing it on first use (after one eager warm-up run, which
@@ -606,7 +625,7 @@ class ModelRunner:
             how = self._sample_or_argmax(seqs, B)
             toks = self._read_tokens(B, lp=how.lp)
             if how.lp:
-                self.last_logprobs = self._records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
+                self.last_logprobs = self.logprobs.records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
             return (toks, self.model.full_logits(B)) if draft_return_logits else toks
         if not last_only:
             self._run_graph(("verify_logits", B), lambda: self._prepare_verify(seqs, ids_from_seq=True), lambda: self._body_verify(B, False))
@@ -621,7 +640,7 @@ class ModelRunner:
         self._log_margins(B, [(s.seq_id, len(s)) for s in seqs])
         toks = self._read_tokens(B, lp=how.lp)
         if how.lp:
-            self.last_logprobs = self._records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
+            self.last_logprobs = self.logprobs.records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
         return (toks, self.model.full_logits(B)) if draft_return_logits else toks
 
     def eagle_acts(self, n: int) -> torch.Tensor:
@@ -671,10 +690,10 @@ class ModelRunner:
         return how, dict(temps=temps, filters=filters, seqs=seqs, seeds=seeds)
 
     def _stage_sampling(self, how: Sampling, temps=None, filters=None, seqs=None, back: int = 0, temps_q=None, ratio_rows=None,
-                        seeds=None) -> None:
-        """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, the
-        penalty tables, the constraints and the guides of `seqs` (back: see _upload_penalties), and the seeds (-1: none).  A greedy
-        batch without penalties, constraints and guides uploads nothing."""
+                        seeds=None, base: int = 0) -> None:
+        """Upload what the tail of `how` reads: temperatures (a ratio verify: the draft's and the ratio rows too), filters, the seeds
+        (-1: none) and what the rules read of `seqs` (back, base: see engine/logit_rules.py).  A greedy batch without rules uploads
+        nothing."""
         if how.sample:
             self._ensure_stochastic()
             self._upload(self.d_temps, list(temps), torch.float32)
@@ -688,15 +707,16 @@ class ModelRunner:
         if how.seed:        # data, not a capture constant: other seeds replay the same graphs
             self._ensure_seed()
             self._upload(self.d_seed, [int(x) for x in seeds], torch.int64)
-        if how.pen:
-            self._upload_penalties(seqs, back)
+        rules = self._rules(how)
         if how.con:
-            self._upload_constraints(seqs, back)
-        if how.gd:
-            self._upload_guides(seqs, back)
-        if how.lp:          # the N of every sequence; -1 = did not ask: the kernels skip its rows
-            self._ensure_logprob(how.pen)
-            self._upload(self.d_lp_ntop, [-1 if getattr(s, "logprobs", None) is None else int(s.logprobs) for s in seqs], torch.int32)
+            self.rules["con"].eos = self.config.eos     # read at every step: an engine can set its EOS after the rule was built
+        for rule in rules:
+            rule.stage(seqs, back, self._stage_set, base)
+        if how.lp:
+            if self.logprobs is None:
+                assert self.tp_size == 1, "log-probabilities need the whole vocabulary on one rank"
+                self.logprobs = Logprobs(self._rule_sizes())
+            self.logprobs.stage(seqs, self._stage_set, how.pen)
 
     def _ensure_seed(self) -> None:
         """Device buffers of csrc/seeded.hip (allocated on first use): a seed per sequence, the slice candidates of every row a body can
@@ -709,66 +729,6 @@ class ModelRunner:
         self.d_seed_pos = torch.zeros(self.seq_cap, dtype=torch.int64, **dev)
         self.d_seed_ws = torch.zeros(HS.sample_seeded_ws_bytes(rows, self.cfg.vocab_size) // 8, dtype=torch.int64, **dev)
 
-    def _ensure_logprob(self, copy: bool) -> None:
-        """Device buffers of csrc/logprob.hip, sized by the model's logit rows, with the pinned mirrors of what the host reads
-        (allocated on first use).  copy: also the raw-row copy a penalised batch picks from (rows x V bf16, on ITS first use)."""
-        R, V = self.model.max_logit_rows, self.cfg.vocab_size
-        dev = dict(device=self.device)
-        if not hasattr(self, "d_lp_ntop"):
-            assert self.tp_size == 1, "log-probabilities need the whole vocabulary on one rank"
-            self.d_lp_ntop = torch.full((self.seq_cap,), -1, dtype=torch.int32, **dev)
-            self.d_lp_lse = torch.zeros(R, dtype=torch.float32, **dev)
-            self.d_lp_out = torch.zeros(R, dtype=torch.float32, **dev)
-            self.d_lp_top_val = torch.zeros(R, HL.MAX_N, dtype=torch.float32, **dev)
-            self.d_lp_top_id = torch.zeros(R, HL.MAX_N, dtype=torch.int32, **dev)
-            self.d_lp_ws = torch.zeros(HL.logprob_rows_ws_bytes(R, V) // 4, dtype=torch.float32, **dev)
-            self.d_lp_raw = None
-            self.h_lp_out = torch.zeros(R, dtype=torch.float32).pin_memory()
-            self.h_lp_top_val = torch.zeros(R, HL.MAX_N, dtype=torch.float32).pin_memory()
-            self.h_lp_top_id = torch.zeros(R, HL.MAX_N, dtype=torch.int32).pin_memory()
-        if copy and self.d_lp_raw is None:
-            self.d_lp_raw = torch.zeros(R, V, dtype=torch.bfloat16, **dev)
-
-    def _logprob_rows(self, rows: int, how: Sampling, rows_per_param: int) -> None:
-        """Behind compute_logits and in front of _rows: log-sum-exp and top entries of the RAW rows.  A penalised batch also keeps a
-        copy of them (penalties rewrite entries a chosen token may sit on; truncation only writes -inf over entries that can no
-        longer be chosen, so the live rows serve there)."""
-        V = self.cfg.vocab_size
-        HL.logprob_rows(self.model.logits, V, rows, V, self.d_lp_ntop, rows_per_param, self.d_lp_lse, self.d_lp_top_val, self.d_lp_top_id,
-                        self.d_lp_ws, raw_copy=self.d_lp_raw if how.pen else None, raw_ld=V if how.pen else 0)
-
-    def _logprob_src(self, how: Sampling) -> torch.Tensor:
-        return self.d_lp_raw if how.pen else self.model.logits
-
-    def _logprob_pick(self, rows: int, how: Sampling) -> None:
-        """d_lp_out = raw log-probability of d_next, row by row (decode and prefill rows: one sequence each)."""
-        V = self.cfg.vocab_size
-        HL.logprob_pick(self._logprob_src(how), V, rows, V, self.d_next, self.d_lp_lse, self.d_lp_ntop, 1, self.d_lp_out)
-
-    def _post_logprobs(self, rows: int) -> None:
-        """Queue the D2H copies of what the host reads, in front of the synchronise the step performs anyway (lse stays on the device)."""
-        self.h_lp_out[:rows].copy_(self.d_lp_out[:rows], non_blocking=True)
-        self.h_lp_top_val[:rows].copy_(self.d_lp_top_val[:rows], non_blocking=True)
-        self.h_lp_top_id[:rows].copy_(self.d_lp_top_id[:rows], non_blocking=True)
-
-    def _records(self, seqs, row_tokens, single: bool = False):
-        """The records of `seqs` from the pinned mirrors (after the synchronise).  row_tokens: per sequence the (row, token) pairs of
-        its tokens, in order; sequences that did not ask get None.  single: one record per sequence instead of a list."""
-        n = 1 + max(r for pairs in row_tokens for r, _ in pairs)
-        lp, tv, ti = self.h_lp_out[:n].tolist(), self.h_lp_top_val[:n].tolist(), self.h_lp_top_id[:n].tolist()
-        out = []
-        for s, pairs in zip(seqs, row_tokens):
-            N = getattr(s, "logprobs", None)
-            if N is None:
-                out.append(None)
-                continue
-            recs = []
-            for r, tok in pairs:
-                k = sum(1 for i in ti[r][:N] if i >= 0)         # min(N, V): slots past the row's entries hold -1 / -inf
-                recs.append({"token_id": int(tok), "logprob": lp[r], "top_ids": ti[r][:k], "top_logprobs": tv[r][:k]})
-            out.append(recs[0] if single else recs)
-        return out
-
     def _filter(self, lg: torch.Tensor, rows: int, rows_per_param: int) -> None:
         """Truncate `rows` sampled rows in place, one parameter set (d_temps, d_top_k, d_top_p, d_min_p) per rows_per_param rows.
         Rows of temperature 0 and rows whose sequence has no filter come back untouched."""
@@ -780,208 +740,14 @@ class ModelRunner:
         """Some sequence of the batch has a penalty or a logit bias (otherwise nothing is uploaded or launched)."""
         return any(getattr(s, "has_penalty", False) for s in seqs)
 
-    def _ensure_penalty(self) -> None:
-        """Device tables of csrc/penalty.hip beside d_top_k, with their pinned staging (allocated on first use)."""
-        if hasattr(self, "d_pen_ids"):
-            return
-        assert self.K + 1 <= HP.MAX_EXTRA + 1, "speculate_k exceeds SSD_PENALTY_MAX_EXTRA"
-        B, L = self.seq_cap, self.config.max_model_len + self.PENALTY_MAX_BIAS
-        dev = dict(device=self.device)
-        self.pen_tab_ld = L
-        self.d_pen_ids = torch.zeros(B, L, dtype=torch.int32, **dev)        # unique token ids of each sequence's history
-        self.d_pen_cnt = torch.zeros(B, L, dtype=torch.int32, **dev)        # (output count << 1) | in prompt
-        self.d_pen_bias = torch.zeros(B, L, dtype=torch.float32, **dev)
-        self.d_pen_len = torch.zeros(B, dtype=torch.int32, **dev)
-        self.d_pen_par = torch.zeros(3, B, dtype=torch.float32, **dev)      # rows: repetition, presence, frequency
-        self._pen_stage = {}
-
-    def _upload_penalties(self, seqs, back: int = 0) -> None:
-        """Stage every sequence's history table and parameters.  back: lookahead entries at the end of token_ids that are not
-        history (the K speculated tokens under verification: the kernel reads those from the round's inputs, row by row)."""
-        self._ensure_penalty()
-        st = self._pen_stage.get(self._stage_set)
-        if st is None:
-            dsts = (self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.d_pen_len, self.d_pen_par)
-            pinned = [torch.zeros(d.shape, dtype=d.dtype).pin_memory() for d in dsts]
-            st = self._pen_stage[self._stage_set] = (pinned, [t.numpy() for t in pinned])
-        pinned, (ids, cnt, bias, lens, par) = st
-        B, L = len(seqs), self.pen_tab_ld
-        for b, s in enumerate(seqs):
-            if not getattr(s, "has_penalty", False):
-                lens[b], par[0, b], par[1, b], par[2, b] = 0, 1.0, 0.0, 0.0
-                continue
-            tab = s.penalty_table(len(s.token_ids) - back)
-            n = len(tab)
-            if n > L:
-                raise ValueError(f"the history of sequence {s.seq_id} ({n} distinct token and logit_bias ids) does not fit the penalty "
-                                 f"table of {L} entries (max_model_len + {self.PENALTY_MAX_BIAS})")
-            if n:
-                vals = np.array(list(tab.values()), dtype=np.float64)
-                ids[b, :n] = np.clip(np.fromiter(tab.keys(), dtype=np.int64, count=n), -1, 2 ** 31 - 1)
-                cnt[b, :n] = (vals[:, 0].astype(np.int64) << 1) | vals[:, 1].astype(np.int64)
-                bias[b, :n] = vals[:, 2]
-            lens[b], par[0, b], par[1, b], par[2, b] = n, s.repetition_penalty, s.presence_penalty, s.frequency_penalty
-        for d, h in zip((self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.d_pen_len), pinned):
-            d[:B].copy_(h[:B], non_blocking=True)
-        self.d_pen_par.copy_(pinned[4], non_blocking=True)
-
-    def _penalize(self, lg: torch.Tensor, rows: int, rows_per_seq: int, form: str | None) -> None:
-        """Adjust `rows` raw logit rows in place with the uploaded tables.  form None: the table alone; "prefix": row j of a sequence
-        also sees inputs 1..j of its K+1 verify inputs (d_ids); "chain": every row also sees the d_step tokens its draft chain has
-        produced so far (d_spec).  Rows of sequences without penalties come back untouched."""
-        V, K = self.cfg.vocab_size, self.K
-        extra = dict(extra=self.d_ids, extra_ld=K + 1) if form == "prefix" else \
-            dict(extra=self.d_spec, extra_ld=K + 1, extra_n=self.d_step) if form == "chain" else {}
-        HP.penalize_rows(lg, V, rows, V, rows_per_seq, self.d_pen_ids, self.d_pen_cnt, self.d_pen_bias, self.pen_tab_ld, self.d_pen_len,
-                         self.d_pen_par[0], self.d_pen_par[1], self.d_pen_par[2], **extra)
-
-    def _ensure_constraint(self) -> None:
-        """Device buffers of csrc/constrain.hip beside the penalty tables, with their pinned staging (allocated on first use)."""
-        if hasattr(self, "d_con_bits"):
-            return
-        assert self.K + 1 <= HC.MAX_EXTRA + 1, "speculate_k exceeds SSD_CONSTRAIN_MAX_EXTRA"
-        B, W = self.seq_cap, HC.mask_words(self.cfg.vocab_size)
-        dev = dict(device=self.device)
-        self.d_con_bits = torch.zeros(B, W, dtype=torch.int32, **dev)                    # allow mask (uint32 words, moved as int32 bits)
-        self.d_con_tok = torch.zeros(B, HC.MAX_WORD_TOKENS, dtype=torch.int32, **dev)    # flattened bad words
-        self.d_con_off = torch.zeros(B, HC.MAX_WORDS + 1, dtype=torch.int32, **dev)
-        self.d_con_stop = torch.zeros(B, HC.MAX_STOP, dtype=torch.int32, **dev)          # stop ids (+ the EOS) held back by min_tokens
-        self.d_con_tail = torch.zeros(B, HC.TAIL_LD, dtype=torch.int32, **dev)           # the last tokens the host knows
-        self.d_con_par = torch.zeros(5, B, dtype=torch.int32, **dev)                     # rows: allow_on, min_left, stop_len, bw_n, tail_len
-        self._con_stage = {}
-        self._con_bits_owner = [None] * B       # the sequence whose mask row b of d_con_bits holds: a request's mask travels once
-
-    def _upload_constraints(self, seqs, back: int = 0) -> None:
-        """Stage every sequence's allow mask, stop list, bad words, tail and counters.  back: lookahead entries at the end of
-        token_ids that the kernel reads from the round's inputs instead (_upload_penalties).  The allow mask (16 KB at a 128 K
-        vocabulary) is a constant of the request: it travels when its sequence takes a batch row it did not have the step before."""
-        self._ensure_constraint()
-        st = self._con_stage.get(self._stage_set)
-        dsts = (self.d_con_bits, self.d_con_tok, self.d_con_off, self.d_con_stop, self.d_con_tail, self.d_con_par)
-        if st is None:
-            pinned = [torch.zeros(d.shape, dtype=d.dtype).pin_memory() for d in dsts]
-            st = self._con_stage[self._stage_set] = (pinned, [t.numpy() for t in pinned])
-        pinned, (bits, tok, off, stop, tail, par) = st
-        B, V, eos = len(seqs), self.cfg.vocab_size, self.config.eos
-        any_words = False
-        for b, s in enumerate(seqs):
-            par[:, b] = 0
-            if not getattr(s, "has_constraint", False):
-                continue
-            upto = len(s.token_ids) - back
-            if s.allowed_token_ids is not None:
-                par[0, b] = 1
-                if self._con_bits_owner[b] != s.seq_id:
-                    self._con_bits_owner[b] = s.seq_id
-                    bits[b] = s.allow_bits(V).view(np.int32)
-                    self.d_con_bits[b].copy_(pinned[0][b], non_blocking=True)
-            if s.min_tokens > 0:
-                stops = s.stop_list(eos)
-                if len(stops) > HC.MAX_STOP:
-                    raise ValueError(f"sequence {s.seq_id} has {len(stops)} stop ids (the EOS included) to hold back under min_tokens: "
-                                     f"at most {HC.MAX_STOP}")
-                stop[b, :len(stops)] = np.clip(stops, -1, 2 ** 31 - 1)
-                par[1, b], par[2, b] = s.min_left(upto), len(stops)
-            if s.bad_words:
-                flat, offs = s.bad_words_flat
-                tok[b, :len(flat)] = np.clip(flat, -1, 2 ** 31 - 1)
-                off[b, :len(offs)] = offs
-                t = s.constraint_tail(HC.TAIL_LD, upto)
-                tail[b, :len(t)] = np.clip(t, -1, 2 ** 31 - 1)
-                par[3, b], par[4, b] = len(s.bad_words), len(t)
-                any_words = True
-        for d, h, on in zip(dsts[1:5], pinned[1:5], (any_words, any_words, True, any_words)):
-            if on:
-                d[:B].copy_(h[:B], non_blocking=True)
-        self.d_con_par.copy_(pinned[5], non_blocking=True)
-
-    def _constrain(self, lg: torch.Tensor, rows: int, rows_per_seq: int, form: str | None) -> None:
-        """Ban entries of `rows` raw logit rows in place with the uploaded constraints; the forms are those of _penalize: "prefix" --
-        row j of a verify also sees inputs 1..j (d_ids), "chain" -- every row also sees the d_step tokens of its draft chain
-        (d_spec).  Rows of sequences without constraints come back untouched."""
-        V, K = self.cfg.vocab_size, self.K
-        extra = dict(extra=self.d_ids, extra_ld=K + 1) if form == "prefix" else \
-            dict(extra=self.d_spec, extra_ld=K + 1, extra_n=self.d_step) if form == "chain" else {}
-        par = self.d_con_par
-        HC.constrain_rows(lg, V, rows, V, rows_per_seq, allow_on=par[0], allow_bits=self.d_con_bits, min_left=par[1],
-                          stop_ids=self.d_con_stop, stop_len=par[2], bw_tok=self.d_con_tok, bw_off=self.d_con_off, bw_n=par[3],
-                          tail=self.d_con_tail, tail_ld=HC.TAIL_LD, tail_len=par[4], **extra)
-
-    def _ensure_guide(self) -> None:
-        """Device tables of csrc/guide.hip: one automaton slot per batch row at the strides of the largest automaton a request may
-        carry, the per-step values and the state of every logit row (allocated on first use)."""
-        if hasattr(self, "d_gd_off"):
-            return
-        assert self.K + 1 <= HG.MAX_EXTRA + 1, "speculate_k exceeds SSD_GUIDE_MAX_EXTRA"
-        B, S, E = self.seq_cap, HG.MAX_STATES, HG.MAX_EDGES
-        dev = dict(device=self.device)
-        self.d_gd_off = torch.zeros(B, S + 1, dtype=torch.int32, **dev)         # CSR offsets
-        self.d_gd_dflt = torch.full((B, S), -1, dtype=torch.int32, **dev)
-        self.d_gd_tok = torch.zeros(B, E, dtype=torch.int32, **dev)
-        self.d_gd_next = torch.zeros(B, E, dtype=torch.int32, **dev)
-        self.d_gd_par = torch.zeros(3, B, dtype=torch.int32, **dev)             # rows: guide_on, state0, n_states
-        self.d_gd_state = torch.full((max(self.model.max_logit_rows, B),), -1, dtype=torch.int32, **dev)
-        self._gd_stage = {}
-        # the sequence whose automaton each slot holds: an automaton (up to 2 MB) travels when its sequence takes a slot it did not
-        # have the step before.  A decode, chain or verify batch uses the slots of its rows, 0 .. n - 1; the eager prefill of B new
-        # requests uses the LAST B slots (_gd_base), which the running batch leaves free while running + new <= max_num_seqs, so an
-        # arrival does not evict the automaton of the sequence decoding in row 0
-        self._gd_owner = [None] * B
-        self._gd_base = 0
-
-    def _upload_guides(self, seqs, back: int = 0) -> None:
-        """Stage guide_on, the state in front of every sequence's first row (Sequence.guide_state: derived from token_ids; back as in
-        _upload_penalties, the kernel walks the round's own tokens) and n_states, every step; the used part of a sequence's tables
-        only when the slot (_gd_base + its row) changes hands, from the pinned copy the sequence keeps (Sequence.guide_pinned: made
-        once per request; the automaton is immutable, so it is never rewritten under a copy in flight)."""
-        self._ensure_guide()
-        st = self._gd_stage.get(self._stage_set)
-        if st is None:
-            pinned = torch.zeros(self.d_gd_par.shape, dtype=torch.int32).pin_memory()
-            st = self._gd_stage[self._stage_set] = (pinned, pinned.numpy())
-        pinned, par = st
-        for b, s in enumerate(seqs):
-            par[:, b] = 0
-            a = getattr(s, "guide", None)
-            if a is None:
-                continue
-            par[0, b], par[1, b], par[2, b] = 1, s.guide_state(len(s.token_ids) - back), a.num_states
-            slot = self._gd_base + b
-            if self._gd_owner[slot] != s.seq_id:
-                self._gd_owner[slot] = s.seq_id
-                n, m = a.num_states, a.num_edges
-                flat, at = s.guide_pinned(), 0
-                for d, k in ((self.d_gd_off, n + 1), (self.d_gd_dflt, n), (self.d_gd_tok, m), (self.d_gd_next, m)):
-                    if k:
-                        d[slot, :k].copy_(flat[at:at + k], non_blocking=True)
-                    at += k
-        self.d_gd_par.copy_(pinned, non_blocking=True)
-
-    def _guide(self, lg: torch.Tensor, rows: int, rows_per_seq: int, form: str | None) -> None:
-        """Ban in place what the automaton state in front of each of `rows` raw logit rows does not allow: the walk from the uploaded
-        states through the tokens the row sees (the forms and buffers of _penalize and _constrain), then the rows kernel.  Rows of
-        sequences without a guide come back untouched."""
-        V, K = self.cfg.vocab_size, self.K
-        extra = dict(extra=self.d_ids, extra_ld=K + 1) if form == "prefix" else \
-            dict(extra=self.d_spec, extra_ld=K + 1, extra_n=self.d_step) if form == "chain" else {}
-        par, o = self.d_gd_par, self._gd_base          # (the per-step values are indexed by the batch row, the tables by the slot)
-        tables = (par[2], self.d_gd_off[o:], self.d_gd_dflt[o:], self.d_gd_tok[o:], self.d_gd_next[o:], HG.MAX_STATES, HG.MAX_EDGES)
-        HG.guide_walk(self.d_gd_state, rows, rows_per_seq, par[0], par[1], *tables, **extra)
-        HG.guide_rows(lg, V, rows, V, self.d_gd_state, rows_per_seq, *tables)
-
     def _sample_or_argmax(self, seqs, B: int) -> Sampling:
         """The prefill's first token, eagerly behind the (possibly replayed) forward; a penalised sequence's history is the prompt."""
         how, values = self._seq_sampling(seqs, prefill=True)
-        if how.gd:          # eager, so the tables' base may differ from the graphs': the last B slots (_ensure_guide)
-            self._ensure_guide()
-            self._gd_base = self.seq_cap - B
-        try:
-            self._stage_sampling(how, **values)
-            if how.lp:
-                self._logprob_rows(B, how, 1)
-            lg = self._rows(B, how)
-        finally:
-            self._gd_base = 0
+        base = self.seq_cap - B     # eager, so the table slots may differ from the graphs': the last B (logit_rules.take_slots)
+        self._stage_sampling(how, **values, base=base)
+        if how.lp:
+            self.logprobs.rows(self.model.logits, B, 1, how.pen)
+        lg = self._rows(B, how, base=base)
         if how.sample:
             if how.seed:    # the token at position len(s): keyed like the decode that would have drawn it
                 self._upload(self.d_seed_pos, [len(s) - 1 for s in seqs], torch.int64)
@@ -989,13 +755,13 @@ class ModelRunner:
         else:
             self._greedy(lg, B, how)
         if how.lp:
-            self._logprob_pick(B, how)
+            self.logprobs.pick(self.model.logits, B, self.d_next, how.pen)
         return how
 
     def _read_tokens(self, n: int, lp: bool = False) -> list[int]:
         self.h_next[:n].copy_(self.d_next[:n], non_blocking=True)
         if lp:
-            self._post_logprobs(n)
+            self.logprobs.post(n)
         torch.cuda.current_stream().synchronize()
         self._check_collectives()
         return self.h_next[:n].tolist()
@@ -1062,10 +828,8 @@ class ModelRunner:
                 logits_q = self._lq_dummy[:B]
             assert logits_q.is_contiguous() and tuple(logits_q.shape) == (B, K, self.cfg.vocab_size)
             if getattr(self, "_lq_ptr", None) not in (None, logits_q.data_ptr()):       # the pointer is baked in the sampling graphs
-                on_off = (False, True)
-                baked = {"verify" + Sampling(True, f, p, l, d, c, g).suffix for f in on_off for p in on_off for l in on_off for d in on_off
-                         for c in on_off for g in on_off}
-                self.graphs = {k: v for k, v in self.graphs.items() if k[0] not in baked}
+                # (the sampled verify graphs: every suffix of a sampling batch starts with "_s", and "verify_logits" does not)
+                self.graphs = {k: v for k, v in self.graphs.items() if not k[0].startswith("verify_s")}
             self._lq_ptr = logits_q.data_ptr()
 
         def stage():
@@ -1078,7 +842,7 @@ class ModelRunner:
         self._log_margins(B * (K + 1), [(s.seq_id, s.num_tokens - (K + 1) + j + 1) for s in seqs for j in range(K + 1)])
         self.h_packed[:B].copy_(self.d_packed[:B], non_blocking=True)
         if how.lp:
-            self._post_logprobs(B * (K + 1))
+            self.logprobs.post(B * (K + 1))
         # the verify is in flight and the host is about to block on it: the moment for a co-located draft server to
         # enqueue its next round on its own stream (engine/draft_runner.py run_deferred)
         hook = getattr(self, "overlap_hook", None)
@@ -1090,7 +854,7 @@ class ModelRunner:
         suffixes = [r[2:3 + r[0]] for r in rows]
         recovery = [r[1] for r in rows]
         if how.lp:          # row (b, j) predicted input j + 1 (accepted while j < a) or, at j = a, the recovery token
-            self.last_logprobs = self._records(seqs, [[(b * (K + 1) + j, r[3 + j] if j < r[0] else r[1]) for j in range(r[0] + 1)]
+            self.last_logprobs = self.logprobs.records(seqs, [[(b * (K + 1) + j, r[3 + j] if j < r[0] else r[1]) for j in range(r[0] + 1)]
                                                       for b, r in enumerate(rows)])
         return suffixes, recovery
 

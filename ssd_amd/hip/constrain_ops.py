@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check
 
 c_void_p, c_int, c_long = C.c_void_p, C.c_int, C.c_long
@@ -27,24 +27,11 @@ CONSTRAIN_SIGNATURES = {
                            c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
 }
 
-_CLIB = None
 LAUNCHES = 0        # constrain_rows calls of this process (eager launches and graph captures; a replay launches without Python)
 
 
 def load_constrain_library():
-    global _CLIB
-    if _CLIB is not None:
-        return _CLIB
-    lib = load_library()
-    for name, args in CONSTRAIN_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _CLIB = lib
-    return lib
+    return bind(CONSTRAIN_SIGNATURES)
 
 
 def mask_words(V: int) -> int:

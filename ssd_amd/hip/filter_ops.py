@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check
 
 c_void_p, c_int, c_long = C.c_void_p, C.c_int, C.c_long
@@ -19,24 +19,11 @@ FILTER_SIGNATURES = {
     "ssd_filter_rows": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
 }
 
-_FLIB = None
 LAUNCHES = 0        # filter_rows calls of this process (eager launches and graph captures; a replay launches without Python)
 
 
 def load_filter_library():
-    global _FLIB
-    if _FLIB is not None:
-        return _FLIB
-    lib = load_library()
-    for name, args in FILTER_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _FLIB = lib
-    return lib
+    return bind(FILTER_SIGNATURES)
 
 
 def filter_rows(logits, ld: int, T: int, V: int, temps, top_k, top_p, min_p, rows_per_param: int, kept=None) -> None:

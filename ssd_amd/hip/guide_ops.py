@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check
 
 c_void_p, c_int, c_long = C.c_void_p, C.c_int, C.c_long
@@ -26,24 +26,11 @@ GUIDE_SIGNATURES = {
                        c_void_p],
 }
 
-_GLIB = None
 LAUNCHES = 0        # guide_walk + guide_rows calls of this process (eager launches and graph captures; a replay launches without Python)
 
 
 def load_guide_library():
-    global _GLIB
-    if _GLIB is not None:
-        return _GLIB
-    lib = load_library()
-    for name, args in GUIDE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _GLIB = lib
-    return lib
+    return bind(GUIDE_SIGNATURES)
 
 
 def guide_walk(state_rows, T: int, rows_per_seq: int, guide_on, state0, n_states, edge_off, dflt, edge_tok, edge_next, states_ld: int,

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check, MODE_CAUSAL
 
 c_void_p, c_int, c_float = C.c_void_p, C.c_int, C.c_float
@@ -25,23 +25,9 @@ KV8_SIGNATURES = {
     "ssd_kv_fp8_dequant": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
 }
 
-_KV8LIB = None
-
 
 def load_kv8_library():
-    global _KV8LIB
-    if _KV8LIB is not None:
-        return _KV8LIB
-    lib = load_library()
-    for name, args in KV8_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _KV8LIB = lib
-    return lib
+    return bind(KV8_SIGNATURES)
 
 
 def rope_store_kv_fp8(qkv_rows, positions, cos_sin, slot_mapping, q_out, k_cache, v_cache, T, nh, nkv, hd, block_size,

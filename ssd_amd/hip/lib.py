@@ -132,6 +132,16 @@ class SsdHipError(RuntimeError):
     pass
 
 
+def _set_signatures(lib, signatures: dict, restypes: dict) -> None:
+    for name, args in signatures.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise SsdHipError(f"libssdhip.so does not export {name}") from e
+        fn.argtypes = args
+        fn.restype = restypes.get(name, c_int)
+
+
 def load_library():
     global _LIB
     if _LIB is not None:
@@ -141,14 +151,21 @@ def load_library():
         raise SsdHipError(f"{path} not found: build it with `make -C ssd_amd/csrc` (or __graft_entry__.build()); "
                           "there is no CPU fallback for the hot path")
     lib = C.CDLL(path)
-    for name, args in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
+    _set_signatures(lib, SIGNATURES, {})
     if lib.ssd_abi_version() != ABI_VERSION:
         raise SsdHipError("libssdhip.so ABI version mismatch")
     _LIB = lib
+    return lib
+
+
+_BOUND: set = set()       # id() of the signature tables bind() has set on the library
+
+
+def bind(signatures: dict, restypes: dict | None = None):
+    """libssdhip.so with the functions of one additive header bound: name -> argtypes as in its `*_ops.py` table, restype int unless
+    `restypes` names another.  A missing symbol raises SsdHipError naming it; a table is set once per process."""
+    lib = load_library()
+    if id(signatures) not in _BOUND:
+        _set_signatures(lib, signatures, restypes or {})
+        _BOUND.add(id(signatures))
     return lib

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind, SsdHipError
 from .ops import _p, _stream, _check
 
 c_void_p, c_int, c_long = C.c_void_p, C.c_int, C.c_long
@@ -26,24 +26,11 @@ LOGPROB_SIGNATURES = {
                                 c_void_p],
 }
 
-_LLIB = None
 LAUNCHES = 0        # kernel-launching calls of this process (eager launches and graph captures; a replay launches without Python)
 
 
 def load_logprob_library():
-    global _LLIB
-    if _LLIB is not None:
-        return _LLIB
-    lib = load_library()
-    for name, args in LOGPROB_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _LLIB = lib
-    return lib
+    return bind(LOGPROB_SIGNATURES)
 
 
 def logprob_rows_ws_bytes(T: int, V: int) -> int:

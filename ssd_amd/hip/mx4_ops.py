@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check, EPI_ROWS
 
 c_void_p, c_int = C.c_void_p, C.c_int
@@ -22,23 +22,9 @@ MX4_SIGNATURES = {
     "ssd_gemm_mxfp4_cfg": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
 }
 
-_MX4LIB = None
-
 
 def load_mx4_library():
-    global _MX4LIB
-    if _MX4LIB is not None:
-        return _MX4LIB
-    lib = load_library()
-    for name, args in MX4_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _MX4LIB = lib
-    return lib
+    return bind(MX4_SIGNATURES)
 
 
 def mx4_rows_to_frag(packed, scale, q_frag, s_frag, N: int, K: int, row_map=None):

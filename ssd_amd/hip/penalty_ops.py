@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check
 
 c_void_p, c_int, c_long = C.c_void_p, C.c_int, C.c_long
@@ -21,24 +21,11 @@ PENALTY_SIGNATURES = {
                           c_void_p, c_void_p, c_int, c_void_p, c_void_p],
 }
 
-_PLIB = None
 LAUNCHES = 0        # penalize_rows calls of this process (eager launches and graph captures; a replay launches without Python)
 
 
 def load_penalty_library():
-    global _PLIB
-    if _PLIB is not None:
-        return _PLIB
-    lib = load_library()
-    for name, args in PENALTY_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _PLIB = lib
-    return lib
+    return bind(PENALTY_SIGNATURES)
 
 
 def pack_count(count: int, in_prompt: bool) -> int:

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check, EPI_ROWS
 
 c_void_p, c_int = C.c_void_p, C.c_int
@@ -21,23 +21,9 @@ QUANT_SIGNATURES = {
     "ssd_gemm_fp8_cfg": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
 }
 
-_QLIB = None
-
 
 def load_quant_library():
-    global _QLIB
-    if _QLIB is not None:
-        return _QLIB
-    lib = load_library()
-    for name, args in QUANT_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _QLIB = lib
-    return lib
+    return bind(QUANT_SIGNATURES)
 
 
 def fp8_rows_to_frag(q_rows, q_frag, N: int, K: int, row_map=None):

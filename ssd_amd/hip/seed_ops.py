@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind, SsdHipError
 from .ops import _p, _stream, _check
 
 c_void_p, c_int, c_long, c_uint, c_float = C.c_void_p, C.c_int, C.c_long, C.c_uint, C.c_float
@@ -27,24 +27,11 @@ SEED_SIGNATURES = {
     "ssd_seeded_uniforms": [c_void_p, c_void_p, c_int, c_int, c_uint, c_int, c_void_p, c_void_p],
 }
 
-_SLIB = None
 LAUNCHES = 0        # kernel-launching calls of this process (eager launches and graph captures; a replay launches without Python)
 
 
 def load_seed_library():
-    global _SLIB
-    if _SLIB is not None:
-        return _SLIB
-    lib = load_library()
-    for name, args in SEED_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_long if name == "ssd_sample_seeded_ws_bytes" else c_int
-    _SLIB = lib
-    return lib
+    return bind(SEED_SIGNATURES, {"ssd_sample_seeded_ws_bytes": c_long})
 
 
 def sample_seeded_ws_bytes(T: int, V: int) -> int:

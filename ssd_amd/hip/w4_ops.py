@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check, EPI_ROWS
 
 c_void_p, c_int = C.c_void_p, C.c_int
@@ -22,23 +22,9 @@ W4_SIGNATURES = {
     "ssd_gemm_w4a16_cfg": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
 }
 
-_W4LIB = None
-
 
 def load_w4_library():
-    global _W4LIB
-    if _W4LIB is not None:
-        return _W4LIB
-    lib = load_library()
-    for name, args in W4_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _W4LIB = lib
-    return lib
+    return bind(W4_SIGNATURES)
 
 
 def w4_rows_to_frag(packed, scale, q_frag, s_frag, N: int, K: int, row_map=None):

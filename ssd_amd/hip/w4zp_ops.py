@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .lib import load_library, SsdHipError
+from .lib import bind
 from .ops import _p, _stream, _check, EPI_ROWS
 
 c_void_p, c_int = C.c_void_p, C.c_int
@@ -23,23 +23,9 @@ W4ZP_SIGNATURES = {
                               c_void_p],
 }
 
-_W4ZPLIB = None
-
 
 def load_w4zp_library():
-    global _W4ZPLIB
-    if _W4ZPLIB is not None:
-        return _W4ZPLIB
-    lib = load_library()
-    for name, args in W4ZP_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SsdHipError(f"libssdhip.so does not export {name}") from e
-        fn.argtypes = args
-        fn.restype = c_int
-    _W4ZPLIB = lib
-    return lib
+    return bind(W4ZP_SIGNATURES)
 
 
 def w4zp_rows_to_frag(packed, scale, zero, q_frag, s_frag, z_frag, N: int, K: int, row_map=None):

@@ -285,7 +285,9 @@ def test_a_request_that_inherits_a_batch_row_is_guided_by_its_own_automaton(engi
     # where the tables went: the prefill used the last slot, the decode (or verify) batch slot 0 -- so the prefill of an arriving
     # request does not evict the automaton of the sequence running in row 0 -- and both hold the last request's
     for r in (eng.model_runner, eng.draft_runner if mode == "sync" else None):
-        if r is not None and hasattr(r, "_gd_owner"):
-            assert r._gd_owner[0] is not None and r._gd_base == 0
+        if r is not None:
+            assert "gd" in r.rules, sorted(r.rules)         # a runner that guided something has the rule object
+            owner = r.rules["gd"].owner
+            assert owner[0] is not None
             if not r.is_draft:          # (a draft's prefill token is never used, so it is not guided)
-                assert r._gd_owner[r.seq_cap - 1] == r._gd_owner[0], r._gd_owner
+                assert owner[r.seq_cap - 1] == owner[0], owner
