@@ -127,7 +127,9 @@ int ssd_gemm_pf(const void* x_frag, const void* w_frag, const void* bias, void* 
  * + SiluAndMul (activation.py:11-14).  x comes either fragment-major (x_frag) or as row-major h (+ res_in) normalised on
  * the fly with norm_w / eps; then res_out (!= res_in) receives bf16(h + res_in).  epilogue: 0 rows, 1 SiLU*mul -> frag,
  * 3 RoPE + KV store (weights from ssd_rows_to_frag_qkv; q_out rows [M][nh*hd], K/V into the paged cache at `slots`).
- * nt / waves <= 0 pick the default decomposition. */
+ * nt / waves <= 0 pick the default decomposition.  Epilogue 0 needs y and ldy >= N; epilogue 1 needs y, N % 64 == 0 (the
+ * output fragment is N / 2 wide), an even nt and no bias (it adds none); epilogue 3 needs block_size > 0.  With the norm
+ * prologue M * K * 2 B plus the combine area must fit 160 KiB of LDS (M = 15 at K = 4096); beyond that: SSD_ERR_SHAPE. */
 int ssd_gemm_fused(const void* x_frag, const void* h_rows, const void* res_in, void* res_out, const void* norm_w, float eps,
                    const void* w_frag, const void* bias, int M, int N, int K, int epilogue, void* y, int ldy,
                    const int64_t* positions, const float* cos_sin, const int32_t* slots, void* q_out, void* k_cache,

@@ -572,7 +572,11 @@ static int fused_impl(const void* x_frag, const void* h_rows, const float* h_par
   const bool m32 = M > 16 && M <= 32 && x_frag && !h_rows && !h_parts && epilogue == FEPI_QKV_ROPE;    // two token tiles
   if (M <= 0 || (M > 16 && !m32) || (N & 15) || (K & 31) || N <= 0 || K <= 0) return SSD_ERR_SHAPE;
   if ((h_rows != nullptr) + (x_frag != nullptr) + (h_parts != nullptr) != 1) return SSD_ERR_ARG;     // exactly one x source
-  if ((h_rows || h_parts) && !norm_w) return SSD_ERR_ARG;
+  if (!w_frag || ((h_rows || h_parts) && !norm_w)) return SSD_ERR_ARG;
+  if ((epilogue == FEPI_ROWS || epilogue == FEPI_SILU_FRAG) && !y) return SSD_ERR_ARG;
+  if (epilogue == FEPI_ROWS && ldy < N) return SSD_ERR_SHAPE;
+  if (epilogue == FEPI_SILU_FRAG && (N & 63)) return SSD_ERR_SHAPE;       // the output fragment is [M][N / 2]: N / 2 in whole k-tiles
+  if (epilogue == FEPI_SILU_FRAG && bias) return SSD_ERR_ARG;             // that epilogue adds no bias: refuse, not ignore
   if (h_parts && (S < 1 || S > 16)) return SSD_ERR_ARG;
   if (res_out && res_out == res_in) return SSD_ERR_ARG;                   // in-place residual would race
   const int groups = N / 16;
@@ -586,7 +590,7 @@ static int fused_impl(const void* x_frag, const void* h_rows, const float* h_par
   if (epilogue == FEPI_SILU_FRAG && (nt & 1)) return SSD_ERR_ARG;
   if (epilogue == FEPI_QKV_ROPE) {
     if (!positions || !cos_sin || !slots || !q_out || !k_cache || !v_cache) return SSD_ERR_ARG;
-    if (hd != 64 && hd != 128 && hd != 256) return SSD_ERR_SHAPE;
+    if ((hd != 64 && hd != 128 && hd != 256) || block_size <= 0) return SSD_ERR_SHAPE;
     if (N != (nh + 2 * nkv) * hd) return SSD_ERR_SHAPE;
   }
   FusedParams p;

@@ -23,7 +23,8 @@ __global__ void embedding_kernel(const int64_t* __restrict__ ids, const u32x4_t*
 
 extern "C" int ssd_embedding(const int64_t* ids, const void* table, void* out_rows, int T, int H,
                              long vocab_start, long vocab_count, void* stream) {
-  if (T <= 0 || H <= 0 || (H & 7)) return SSD_ERR_SHAPE;
+  if (T <= 0 || H <= 0 || (H & 7) || vocab_count <= 0) return SSD_ERR_SHAPE;
+  if (!ids || !table || !out_rows) return SSD_ERR_ARG;
   int threads = H / 8; if (threads > 256) threads = 256; if (threads < 64) threads = 64;
   hipLaunchKernelGGL(embedding_kernel, dim3(T), dim3(threads), 0, (hipStream_t)stream, ids,
                      (const u32x4_t*)table, (u32x4_t*)out_rows, H / 8, vocab_start, vocab_count);
@@ -130,6 +131,7 @@ rmsnorm_kernel(const u32x4_t* __restrict__ x, const u32x4_t* __restrict__ res_in
 extern "C" int ssd_rmsnorm(const void* x_rows, const void* res_in, void* res_out, const void* weight, float eps,
                            void* out_rows, void* out_frag, const int32_t* gather_rows, int T, int H, void* stream) {
   if (T <= 0 || H <= 0 || (H & 31) || H > NORM_MAXH) return SSD_ERR_SHAPE;
+  if (!x_rows || !weight || (!out_rows && !out_frag && !res_out)) return SSD_ERR_ARG;
   if (ssd_norm_threads(H) == 1024)
     hipLaunchKernelGGL(rmsnorm_kernel<1024>, dim3(T), dim3(1024), 0, (hipStream_t)stream, (const u32x4_t*)x_rows,
                        (const u32x4_t*)res_in, (u32x4_t*)res_out, (const u32x4_t*)weight, eps, (u32x4_t*)out_rows,
@@ -213,7 +215,7 @@ extern "C" int ssd_rmsnorm_pair(const void* x0_rows, const void* weight0, const 
 extern "C" int ssd_rmsnorm_parts(const void* parts, int splits, int slab_rows, const void* res_in, void* res_out,
                                  const void* weight, float eps, void* out_rows, void* out_frag, int T, int H, void* stream) {
   if (T <= 0 || H <= 0 || (H & 31) || H > NORM_MAXH || splits < 1 || splits > 16 || slab_rows < T) return SSD_ERR_SHAPE;
-  if (!parts) return SSD_ERR_ARG;
+  if (!parts || !weight || (!out_rows && !out_frag && !res_out)) return SSD_ERR_ARG;
   if (ssd_norm_threads(H) == 1024)
     hipLaunchKernelGGL(rmsnorm_kernel<1024>, dim3(T), dim3(1024), 0, (hipStream_t)stream, (const u32x4_t*)nullptr,
                        (const u32x4_t*)res_in, (u32x4_t*)res_out, (const u32x4_t*)weight, eps, (u32x4_t*)out_rows,
