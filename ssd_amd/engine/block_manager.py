@@ -85,7 +85,9 @@ class BlockManager:
     def allocate(self, seq) -> None:
         table = self._table(seq)
         assert not table
-        h, missed = -1, not self.prefix_cache
+        # a sequence whose prompt is still to be scored (SamplingParams.prompt_logprobs) needs every row of it computed: the target
+        # gives it fresh blocks, and still hashes and registers its full blocks below, so later requests hit them
+        h, missed = -1, not self.prefix_cache or (not self.is_draft and getattr(seq, "needs_prompt_logprobs", False))
         for i in range(seq.num_blocks):
             toks = seq.block(i)
             h = self.compute_hash(toks, h) if len(toks) == self.block_size else -1

@@ -3,6 +3,7 @@
 Public behaviour kept: ``LLM(model, **Config fields)``; ``generate(prompts, sampling_params, use_tqdm=True,
 stream_callback=None) -> (outputs, METRICS)`` with ``outputs[i] = {"text", "token_ids"}``; the METRICS keys.  A request with
 ``SamplingParams(logprobs=N)`` also gets ``"logprobs"`` (one record per token) and ``"cumulative_logprob"``; one with
+``SamplingParams(prompt_logprobs=N)`` also gets ``"prompt_logprobs"`` (one entry per prompt token, the first None); one with
 ``SamplingParams(stop_token_ids=[...])`` also gets ``"stop_reason"`` (the stop id that ended it, or None).
 
 Process model (differs by design): one process per GPU, SPMD.  Under ``torchrun`` every rank constructs the same
@@ -99,6 +100,7 @@ class LLMEngine:
         self.draft_runner = None
         self._capped_ids: set[int] = set()
         self._logprobs_out: dict[int, list] = {}        # seq id -> the records of a finished request that asked (step() fills it)
+        self._prompt_logprobs_out: dict[int, list] = {}     # seq id -> the prompt records of a finished request that asked (likewise)
         self._stop_out: dict[int, int | None] = {}      # seq id -> stop_reason of a finished request that set stop_token_ids (likewise)
         self.async_link = None
         self.draft_server = None
@@ -204,6 +206,15 @@ class LLMEngine:
             if getattr(runner, "tp_size", 1) > 1:
                 raise ValueError(f"logprobs is not supported with a tensor-parallel target (tp_size = {runner.tp_size}): every rank "
                                  f"holds a shard of the vocabulary")
+        if sp is not None and sp.prompt_logprobs is not None:
+            # the target's prefill scores the prompt rows (csrc/prompt_logprob.hip); the draft is not involved, and a tensor-parallel
+            # target refuses for the reason above
+            runner = getattr(self, "model_runner", None)
+            self._refuse([r for r in both if r is runner], "supports_prompt_logprobs", ["prompt_logprobs"],
+                         "this runner has no prompt log-probability kernel")
+            if getattr(runner, "tp_size", 1) > 1:
+                raise ValueError(f"prompt_logprobs is not supported with a tensor-parallel target (tp_size = {runner.tp_size}): every "
+                                 f"rank holds a shard of the vocabulary")
         if sp is not None and sp.seed is not None:      # a seeded request draws from its own stream (csrc/seeded.hip), draft included
             self._refuse(both, "supports_seed", ["seed"], "this runner has no per-request random stream")
         active = sp.active_constraints if sp is not None else []
@@ -272,6 +283,8 @@ class LLMEngine:
                 self._logprobs_out[s.seq_id] = s.completion_logprobs
             if s.stop_token_ids:
                 self._stop_out[s.seq_id] = None
+            if s.prompt_logprobs is not None:
+                self._prompt_logprobs_out[s.seq_id] = s.prompt_logprob_records
             if s.first_token_streamed is not None:      # streamed at the prefill, capped before the round that appends it:
                 toks = toks + [s.first_token_streamed]  # the result must carry what the stream already delivered
                 if s.logprobs is not None:              # ... and that token's record
@@ -293,6 +306,8 @@ class LLMEngine:
                 self._logprobs_out[s.seq_id] = s.completion_logprobs
             if s.is_finished and s.stop_token_ids:
                 self._stop_out[s.seq_id] = s.stop_reason
+            if s.is_finished and s.prompt_logprobs is not None:
+                self._prompt_logprobs_out[s.seq_id] = s.prompt_logprob_records
         return capped + [(s.seq_id, s.completion_token_ids) for s in seqs if s.is_finished]
 
     def is_finished(self) -> bool:
@@ -383,6 +398,7 @@ class LLMEngine:
             METRICS[k] = v
         self._capped_ids.clear()            # finish reasons are per generate() call
         self._logprobs_out.clear()
+        self._prompt_logprobs_out.clear()
         self._stop_out.clear()
         if not isinstance(sampling_params, list):
             sampling_params = [sampling_params] * len(prompts)
@@ -443,6 +459,8 @@ class LLMEngine:
                 assert len(records) == len(toks), (len(records), len(toks))
                 result[-1]["logprobs"] = records
                 result[-1]["cumulative_logprob"] = float(sum(r["logprob"] for r in records))
+            if seq_id in self._prompt_logprobs_out:     # SamplingParams(prompt_logprobs=N): one entry per prompt token, the first None
+                result[-1]["prompt_logprobs"] = self._prompt_logprobs_out[seq_id]
             if seq_id in self._stop_out:            # SamplingParams(stop_token_ids=...): the stop id that ended the request, or None
                 result[-1]["stop_reason"] = self._stop_out[seq_id]
         if not stream_callback and self.config.verbose:

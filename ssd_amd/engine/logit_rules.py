@@ -11,7 +11,7 @@ everything else.  The runner builds one on the first batch that needs it and the
     row also sees the tokens of its draft chain so far).  Rows of sequences without the rule come back untouched.
 The host packing of each is a function over numpy arrays (`pack_*`): the classes call it on the views of their pinned buffers, the
 CPU tests on plain arrays.  `Logprobs` (csrc/logprob.hip) reads the raw rows before the rules and picks after the token, so it has an
-interface of its own.
+interface of its own, and `PromptLogprobs` (csrc/prompt_logprob.hip) scores the rows of a prefill that no rule ever touches.
 """
 from __future__ import annotations
 
@@ -24,6 +24,7 @@ from ssd_amd.hip import penalty_ops as HP
 from ssd_amd.hip import constrain_ops as HC
 from ssd_amd.hip import guide_ops as HG
 from ssd_amd.hip import logprob_ops as HL
+from ssd_amd.hip import prompt_logprob_ops as HPL
 
 I32_MAX = 2 ** 31 - 1
 
@@ -314,4 +315,88 @@ class Logprobs:
                 k = sum(1 for i in ti[r][:N] if i >= 0)         # min(N, V): slots past the row's entries hold -1 / -inf
                 recs.append({"token_id": int(tok), "logprob": lp[r], "top_ids": ti[r][:k], "top_logprobs": tv[r][:k]})
             out.append(recs[0] if single else recs)
+        return out
+
+
+class PromptLogprobs:
+    """Raw log-probabilities and ranks of the prompt tokens of a prefill (SamplingParams.prompt_logprobs): `stage` uploads the N of
+    every ROW, `chunk` scores one chunk of rows from its logits, `post` queues the copies the host reads and `records` turns them into
+    the requests' lists.  Row t of a prefill holds the distribution that predicts the token of row t + 1, so the token array is the
+    prefill's own id array one row on; the last row of every sequence predicts the generated token (logprobs= covers it) and is
+    skipped, as is every row of a sequence that does not ask."""
+
+    def __init__(self, z: RuleSizes, max_rows: int):
+        R = max_rows            # max_num_batched_tokens: the rows one prefill can have
+        dev = dict(device=z.device)
+        self.V = z.vocab
+        self.d_ntop = torch.full((R,), -1, dtype=torch.int32, **dev)
+        self.d_rows = torch.arange(R, dtype=torch.int32, **dev)       # the consecutive row indices a chunk's norm gathers
+        self.d_lse = torch.zeros(R, dtype=torch.float32, **dev)
+        self.d_out = torch.zeros(R, dtype=torch.float32, **dev)
+        self.d_rank = torch.zeros(R, dtype=torch.int32, **dev)
+        self.d_top_val = torch.zeros(R, HL.MAX_N, dtype=torch.float32, **dev)
+        self.d_top_id = torch.zeros(R, HL.MAX_N, dtype=torch.int32, **dev)
+        self.h_out = torch.zeros(R, dtype=torch.float32).pin_memory()
+        self.h_rank = torch.zeros(R, dtype=torch.int32).pin_memory()
+        self.h_top_val = torch.zeros(R, HL.MAX_N, dtype=torch.float32).pin_memory()
+        self.h_top_id = torch.zeros(R, HL.MAX_N, dtype=torch.int32).pin_memory()
+        self._staging = Staging((self.d_ntop,))
+        self.chunk_rows = 0     # the chunk buffers exist for this many rows (made on first use, remade when the runner's size changes)
+        self.d_logits = self.d_frag = self.d_ws = None
+
+    @staticmethod
+    def row_counts(seqs, starts) -> list[int]:
+        """n_top of every row of a prefill whose sequence b owns rows starts[b] .. starts[b + 1]: the sequence's N, -1 at its last
+        row and at every row of a sequence that does not need its prompt scored."""
+        ntop = []
+        for b, s in enumerate(seqs):
+            n = starts[b + 1] - starts[b]
+            ask = getattr(s, "needs_prompt_logprobs", False)
+            ntop.extend([int(s.prompt_logprobs) if ask else -1] * (n - 1) + [-1])
+        return ntop
+
+    def stage(self, ntop: list[int], stage_set: int) -> None:
+        (pinned,), (view,) = self._staging.set(stage_set)
+        T = len(ntop)
+        view[:T] = ntop
+        self.d_ntop[:T].copy_(pinned[:T], non_blocking=True)
+
+    def buffers(self, chunk_rows: int, h: int, frag_numel: int):
+        """(norm output fragment, logits) of a chunk of up to chunk_rows rows."""
+        if self.chunk_rows != chunk_rows:
+            dev = dict(device=self.d_lse.device)
+            self.d_logits = torch.zeros(chunk_rows, self.V, dtype=torch.bfloat16, **dev)
+            self.d_frag = torch.zeros(frag_numel, dtype=torch.bfloat16, **dev)
+            self.d_ws = torch.zeros(HPL.logprob_known_ws_bytes(chunk_rows, self.V) // 4, dtype=torch.float32, **dev)
+            self.chunk_rows = chunk_rows
+        return self.d_frag, self.d_logits
+
+    def chunk(self, r0: int, n: int, ids: torch.Tensor) -> None:
+        """Score rows r0 .. r0 + n of the prefill from the chunk's logits; ids: the prefill's int64 id array."""
+        V = self.V
+        HPL.logprob_rows_known(self.d_logits, V, n, V, self.d_ntop[r0:], ids[r0 + 1:], self.d_lse[r0:], self.d_top_val[r0:],
+                               self.d_top_id[r0:], self.d_out[r0:], self.d_rank[r0:], self.d_ws)
+
+    def post(self, rows: int) -> None:
+        """Queue the D2H copies of what the host reads, in front of the synchronise the prefill performs anyway."""
+        for h, d in ((self.h_out, self.d_out), (self.h_rank, self.d_rank), (self.h_top_val, self.d_top_val), (self.h_top_id, self.d_top_id)):
+            h[:rows].copy_(d[:rows], non_blocking=True)
+
+    def records(self, seqs, starts, scored: bool = True):
+        """Per sequence that needs them the list for its prompt -- None, then one record per further prompt token -- from the pinned
+        mirrors (after the synchronise); None for the others.  scored = False: no row was scored (one-token prompts only)."""
+        T = starts[-1]
+        if scored:
+            lp, rk, tv, ti = self.h_out[:T].tolist(), self.h_rank[:T].tolist(), self.h_top_val[:T].tolist(), self.h_top_id[:T].tolist()
+        out = []
+        for b, s in enumerate(seqs):
+            if not getattr(s, "needs_prompt_logprobs", False):
+                out.append(None)
+                continue
+            N, recs = s.prompt_logprobs, [None]
+            for i in range(1, starts[b + 1] - starts[b]):
+                r = starts[b] + i - 1
+                k = sum(1 for j in ti[r][:N] if j >= 0)
+                recs.append({"token_id": int(s[i]), "logprob": lp[r], "rank": rk[r], "top_ids": ti[r][:k], "top_logprobs": tv[r][:k]})
+            out.append(recs)
         return out

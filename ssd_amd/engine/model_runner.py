@@ -28,7 +28,7 @@ from ssd_amd.model_config import ModelConfig
 from ssd_amd import weights as W
 from ssd_amd.utils.graphs import capture
 from ssd_amd.engine.async_proto import to_device
-from ssd_amd.engine.logit_rules import RULES, Logprobs, Penalties, RuleSizes
+from ssd_amd.engine.logit_rules import RULES, Logprobs, Penalties, PromptLogprobs, RuleSizes
 
 
 class Sampling(NamedTuple):
@@ -68,10 +68,13 @@ class ModelRunner:
     supports_logit_filters = True   # top_k / top_p / min_p (csrc/filter.hip); LLMEngine.add_request refuses them on runners without it
     supports_logit_penalties = True # repetition / presence / frequency penalty, logit_bias (csrc/penalty.hip); refused likewise
     supports_logprobs = True        # SamplingParams(logprobs=N): raw log-probabilities of the target's rows (csrc/logprob.hip); likewise
+    supports_prompt_logprobs = True # SamplingParams(prompt_logprobs=N): the prompt rows of the target's prefill (csrc/prompt_logprob.hip); likewise
     supports_seed = True            # SamplingParams(seed=S): the request's own random stream (csrc/seeded.hip); likewise
     supports_logit_constraints = True   # min_tokens / allowed_token_ids / bad_words_ids (csrc/constrain.hip); likewise
     supports_guided_decoding = True     # guided_automaton / guided_choice_ids (csrc/guide.hip); likewise
     PENALTY_MAX_BIAS = Penalties.MAX_BIAS       # logit_bias entries one request may carry
+
+    PROMPT_LOGPROB_ROWS = 512       # default of prompt_logprob_rows: the fastest of 128 / 256 / 512 per prompt row ("Prompt log-probabilities")
 
     def __init__(self, config, model_cfg: ModelConfig, *, is_draft: bool, device: torch.device, tp_rank: int = 0,
                  tp_size: int = 1, tp_group=None, model_path: str | None = None, weights_seed: int = 0,
@@ -182,6 +185,11 @@ class ModelRunner:
         self.last_logprobs = None
         self.rules: dict = {}       # Sampling field -> the rule object of engine/logit_rules.py, built by the first batch that needs it
         self.logprobs = None        # likewise its Logprobs
+        # SamplingParams(prompt_logprobs=N): per sequence of the last prefill the list for its prompt, or None (did not need one)
+        self.last_prompt_logprobs = None
+        self.prompt_logprobs = None     # its PromptLogprobs, built by the first prefill that needs it
+        # rows per chunk of the prompt pass (norm + LM head + kernel): its logits are prompt_logprob_rows x V bf16, taken on first use
+        self.prompt_logprob_rows = self.PROMPT_LOGPROB_ROWS
 
     def _setup_custom_ar(self, want: bool | None) -> None:
         """Enable the one-shot all-reduce for the small TP sums when (a) tensor parallelism is on, (b) it is not
@@ -583,18 +591,21 @@ class ModelRunner:
         B = len(seqs)
         if is_prefill and B > self.seq_cap:
             assert not draft_return_logits
-            toks, acts, lps = [], [], []
+            toks, acts, lps, plps = [], [], [], []
             for i in range(0, B, self.seq_cap):
                 part = seqs[i:i + self.seq_cap]
                 toks.extend(self.run(part, True, last_only))
                 lps.extend(self.last_logprobs or [None] * len(part))
+                plps.extend(self.last_prompt_logprobs or [None] * len(part))
                 if self.model.acts is not None:         # EAGLE-3 taps: the static buffer only holds the last slice
                     acts.append(self.model.acts[:sum(len(s) - s.num_cached_tokens for s in part)].clone())
             self._acts_sliced = torch.cat(acts, dim=0) if acts else None
             self.last_logprobs = lps if any(r is not None for r in lps) else None
+            self.last_prompt_logprobs = plps if any(r is not None for r in plps) else None
             return toks
         self._acts_sliced = None
         self.last_logprobs = None
+        self.last_prompt_logprobs = None
         if is_prefill:
             T, max_q = self._prepare_prefill(seqs)
 
@@ -609,7 +620,14 @@ class ModelRunner:
             # ones replay.  A few graphs are kept, the oldest is dropped.
             key = ("prefill", B, T, max_q)
             full = (*key, self._ctx_hint)
-            if self.config.enforce_eager or T > self.PREFILL_GRAPH_MAX_T:
+            # a prefill that must score prompt rows runs eagerly and is never captured: forward, the prompt pass over its rows,
+            # then the usual last-row logits
+            prompt_lp = not self.is_draft and any(getattr(s, "needs_prompt_logprobs", False) for s in seqs)
+            if prompt_lp:
+                self.model.forward(self.d_ids, self.d_pos, T, self._meta("prefill", B, max_q))
+                starts = self._prompt_pass(seqs, T)
+                self.model.compute_logits(T, gather=self.d_gather, rows=B)
+            elif self.config.enforce_eager or T > self.PREFILL_GRAPH_MAX_T:
                 body()
             elif full not in self.graphs and self._prefill_seen.get(full, 0) < 1:
                 if len(self._prefill_seen) >= 4096:
@@ -626,6 +644,8 @@ class ModelRunner:
             toks = self._read_tokens(B, lp=how.lp)
             if how.lp:
                 self.last_logprobs = self.logprobs.records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
+            if prompt_lp:
+                self.last_prompt_logprobs = self.prompt_logprobs.records(seqs, starts, scored=max(self._prompt_ntop) >= 0)
             return (toks, self.model.full_logits(B)) if draft_return_logits else toks
         if not last_only:
             self._run_graph(("verify_logits", B), lambda: self._prepare_verify(seqs, ids_from_seq=True), lambda: self._body_verify(B, False))
@@ -642,6 +662,35 @@ class ModelRunner:
         if how.lp:
             self.last_logprobs = self.logprobs.records(seqs, [[(b, t)] for b, t in enumerate(toks)], single=True)
         return (toks, self.model.full_logits(B)) if draft_return_logits else toks
+
+    def _prompt_pass(self, seqs, T: int) -> list[int]:
+        """Behind the forward of a prefill of T rows: log-probabilities, ranks and top entries of the prompt tokens of the sequences
+        that need them (engine/logit_rules.py PromptLogprobs), chunk by chunk -- final norm of the chunk's rows, LM head into the
+        chunk's logits, one kernel launch -- with the D2H copies queued behind the last chunk.  A chunk in which no row asks is not
+        computed.  Returns the first row of every sequence (and T)."""
+        assert self.tp_size == 1, "prompt log-probabilities need the whole vocabulary on one rank"
+        starts = [0]
+        for s in seqs:
+            assert s.num_cached_tokens == 0 or not s.needs_prompt_logprobs, "a sequence whose prompt is scored takes no prefix hit"
+            starts.append(starts[-1] + len(s) - s.num_cached_tokens)
+        assert starts[-1] == T
+        P = self.prompt_logprobs
+        if P is None:
+            P = self.prompt_logprobs = PromptLogprobs(self._rule_sizes(), self.d_ids.numel())
+        ntop = self._prompt_ntop = P.row_counts(seqs, starts)
+        if max(ntop) < 0:           # one-token prompts only: nothing to score
+            return starts
+        P.stage(ntop, self._stage_set)
+        C = min(int(self.prompt_logprob_rows), self.d_ids.numel())      # (no chunk is larger than a prefill can be)
+        frag, logits = P.buffers(C, self.model.h, H.frag_numel(C, self.model.h))
+        for r0 in range(0, T - 1, C):       # (the last row of a prefill is some sequence's last row: never scored)
+            n = min(C, T - 1 - r0)
+            if max(ntop[r0:r0 + n]) < 0:
+                continue
+            self.model.compute_logits_into(P.d_rows[r0:], n, frag, logits)
+            P.chunk(r0, n, self.d_ids)
+        P.post(T - 1)
+        return starts
 
     def eagle_acts(self, n: int) -> torch.Tensor:
         """[n, taps * h] tapped activations of the last prefill / verify forward (reference model_runner.py:613-616); a view

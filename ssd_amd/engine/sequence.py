@@ -64,6 +64,11 @@ class Sequence:
         self.logprobs = sp.logprobs
         self.logprob_records: list[dict] = []
         self.recovery_logprob: dict | None = None
+        # prompt log-probabilities (include/ssd_hip_prompt_logprob.h): the N asked for (None = off) and, once the first prefill has
+        # scored the request's own prompt, one entry per prompt token -- None for token 0, then {"token_id", "logprob", "rank",
+        # "top_ids", "top_logprobs"}.  Stored once: the re-prefill after a preemption finds them and does not ask again
+        self.prompt_logprobs = sp.prompt_logprobs
+        self.prompt_logprob_records: list | None = None
         # per-request seed (include/ssd_hip_seed.h; None = the engine's stream).  The stream is keyed by absolute positions, so a
         # preempted sequence's recomputed prefill draws the numbers the position always had
         self.seed = sp.seed
@@ -106,6 +111,16 @@ class Sequence:
     def has_penalty(self) -> bool:
         return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
                 or bool(self.logit_bias))
+
+    @property
+    def needs_prompt_logprobs(self) -> bool:
+        """The next prefill must score the prompt: the request asked and has no records yet.  While this holds the target's block
+        manager gives the sequence no prefix hit (BlockManager.allocate), so every row to be scored is computed."""
+        return self.prompt_logprobs is not None and self.prompt_logprob_records is None
+
+    def store_prompt_logprobs(self, records: list) -> None:
+        assert self.needs_prompt_logprobs and len(records) == self.num_request_prompt_tokens
+        self.prompt_logprob_records = records
 
     @property
     def has_constraint(self) -> bool:

@@ -7,6 +7,14 @@ from ssd_amd.engine.speculate_types import SpeculatorBase, VerifierBase, VerifyR
 from ssd_amd.utils import profiling as prof
 
 
+def store_prompt_logprobs(seqs, runner) -> None:
+    """After the target's prefill of `seqs`: the prompt records the runner left for those that still needed them."""
+    if any(s.needs_prompt_logprobs for s in seqs):
+        for s, recs in zip(seqs, runner.last_prompt_logprobs):
+            if s.needs_prompt_logprobs:
+                s.store_prompt_logprobs(recs)
+
+
 class InferenceStep(ABC):
     def __init__(self, scheduler):
         self.scheduler = scheduler
@@ -26,6 +34,8 @@ class AutoRegressiveStep(InferenceStep):
 
     def _step(self, seqs, is_prefill: bool) -> int:
         token_ids = self.model_runner.call("run", seqs, is_prefill)
+        if is_prefill:
+            store_prompt_logprobs(seqs, self.model_runner)
         if any(s.logprobs is not None for s in seqs):       # the records of those tokens, left beside them by the runner
             self.scheduler.postprocess(seqs, token_ids, is_prefill, logprobs=self.model_runner.last_logprobs)
         else:

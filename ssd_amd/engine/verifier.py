@@ -6,6 +6,7 @@ from __future__ import annotations
 from time import perf_counter
 
 from ssd_amd.engine.speculate_types import SpeculateResult, VerifierBase, VerifyResult
+from ssd_amd.engine.step import store_prompt_logprobs
 from ssd_amd.utils import profiling as prof
 
 
@@ -20,6 +21,7 @@ class Verifier(VerifierBase):
 
     def prefill(self, seqs, eagle: bool = False) -> VerifyResult:
         token_ids = self.target_model_runner.call("run", seqs, True)
+        store_prompt_logprobs(seqs, self.target_model_runner)
         acts = None
         if eagle:       # verifier.py:34-46: the tapped activations of every prompt token; the last one conditions the recovery token
             for s in seqs:

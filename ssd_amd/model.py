@@ -896,6 +896,14 @@ class HipDecoder:
             self._gemm(self.buf_lastf, self.h, self.w["lm_head.weight"], self.V, self.logits, n, self.V)
         return n
 
+    def compute_logits_into(self, gather: torch.Tensor, n: int, frag: torch.Tensor, out: torch.Tensor) -> None:
+        """The same for the n rows `gather` names of the forward that has just run, into the caller's buffers: norm output fragment
+        `frag`, logits `out` [n][V] (the prompt log-probability pass walks a prefill's rows in chunks).  The final norm can be run again
+        and again: a varlen prefill hands over rows (buf_h), and the norm only reads them and the residual."""
+        assert self._last is None and self.tp_size == 1, "the prompt pass needs the row hand-off of a single-rank prefill"
+        self._add_norm(None, n, self.w["model.norm.weight"], res_in=self.buf_res, out_frag=frag, gather=gather)
+        self._gemm(frag, self.h, self.w["lm_head.weight"], self.V, out, n, self.V)
+
     def _ap_ok(self, n: int) -> bool:
         """compute_logits(n) leaves argmax candidates for its n rows."""
         return self.argmax_fused and n <= self.ap_rows

@@ -6,6 +6,12 @@ before the temperature, repetition / presence / frequency penalties and logit bi
 position (N = 1..20).  They are RAW log-probabilities: log_softmax of the target's bf16 logits, taken before penalties, logit bias,
 temperature and truncation (include/ssd_hip_logprob.h) -- whatever the decoding mode, the target's distribution.
 
+``prompt_logprobs=N`` asks the same of the request's own prompt: for every prompt token but the first its raw log-probability under the
+target's distribution at the position in front of it, its rank there (1 = the most probable token; ties count against it, as in vLLM)
+and, for N = 1..20, the N most probable tokens of that position (include/ssd_hip_prompt_logprob.h).  The request's output gains the key
+``"prompt_logprobs"``: a list as long as the prompt whose element 0 is None.  The prompt is then scored in the prefill that computes
+it, so the request takes no prefix-cache hit (later requests still hit the blocks it leaves).
+
 ``seed=S`` makes a sampled request reproducible: every random number it consumes comes from a stream keyed by (S, absolute token
 position, purpose, vocabulary index) (include/ssd_hip_seed.h) instead of the engine's own, which depends on what was sampled before and
 on the batch slot.  It has no effect at temperature 0.
@@ -64,6 +70,7 @@ class SamplingParams:
     frequency_penalty: float = 0.0      # subtracted per occurrence in the output; 0.0 = off
     logit_bias: dict | None = None      # token id -> value in [-100, 100] added to that token's logit; None = off
     logprobs: int | None = None         # None = off; 0 = each generated token's raw log-probability; 1..20 = also the N most probable
+    prompt_logprobs: int | None = None  # None = off; 0 = each prompt token's raw log-probability and rank; 1..20 = also the N most probable
     seed: int | None = None             # None = off (the engine's stream); 0 <= seed < 2**63: the request draws from its own stream
     stop_token_ids: list | None = None      # generation ends when one of these ids is emitted (it stays in token_ids); None = off
     min_tokens: int = 0                     # the EOS and the stop ids cannot be generated before this many output tokens; 0 = off
@@ -97,6 +104,9 @@ class SamplingParams:
         if self.logprobs is not None and (isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int)
                                           or not 0 <= self.logprobs <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be None (off) or an integer in [0, {MAX_LOGPROBS}], got {self.logprobs!r}")
+        if self.prompt_logprobs is not None and (isinstance(self.prompt_logprobs, bool) or not isinstance(self.prompt_logprobs, int)
+                                                 or not 0 <= self.prompt_logprobs <= MAX_LOGPROBS):
+            raise ValueError(f"prompt_logprobs must be None (off) or an integer in [0, {MAX_LOGPROBS}], got {self.prompt_logprobs!r}")
         if self.seed is not None and (isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 2 ** 63):
             raise ValueError(f"seed must be None (off) or an integer in [0, 2**63), got {self.seed!r}")
         if self.stop_token_ids is not None:
