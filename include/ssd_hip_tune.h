@@ -22,8 +22,9 @@ int ssd_gemm_wf_cfg(const void* x_frag, const void* w_frag, const void* bias, vo
 
 
 /* ssd_gemm_pf with an explicit decomposition: nt = 16-row groups per wave (2 or 4; a workgroup owns 4*nt), splits of K.
- * M <= 128: ldy >= N for SSD_EPI_ROWS, and N % 64 == 0 for SSD_EPI_SILU_FRAG (3-, 5- and 7-wave workgroups admit other N).
- * M > 128: nt bits 0..7 select the long-prefill tile form -- 0 default, 1 = 256 x rows x 256 W rows (8 waves), 2 = 128 x 256
+ * Every M: ldy >= N for SSD_EPI_ROWS (else SSD_ERR_SHAPE, before the operands are looked at).
+ * M <= 128: N % 64 == 0 for SSD_EPI_SILU_FRAG (3-, 5- and 7-wave workgroups admit other N).
+ * M > 128: N % 128 == 0; nt bits 0..7 select the long-prefill tile form -- 0 default, 1 = 256 x rows x 256 W rows (8 waves), 2 = 128 x 256
  * (8 waves), 3 = 256 x 128 (8 waves), 4 = 128 x 128 (4 waves); the other bits are ignored; splits <= 0 = the default split of the
  * default form, 1 for any other form; splits must divide K / 64. */
 int ssd_gemm_pf_cfg(const void* x_frag, const void* w_frag, const void* bias, void* y, int M, int N, int K, int ldy,

@@ -551,6 +551,7 @@ static int lm_gemm(const void* x_frag, const void* w_frag, const void* bias, voi
                    void* workspace, int64_t workspace_bytes, int form, int splits, hipStream_t st) {
   if (M > LM_MAX_M || N <= 0 || K <= 0 || N % 128 != 0 || K % 128 != 0) return SSD_ERR_SHAPE;
   if (epilogue != PF_EPI_ROWS && epilogue != PF_EPI_SILU_FRAG) return SSD_ERR_ARG;     // PF_EPI_PARTIALS: M <= 128 only
+  if (epilogue == PF_EPI_ROWS && ldy < N) return SSD_ERR_SHAPE;    // rows would overlap, the last one past the end of y
   if (form < 0 || form > LM_FORMS) return SSD_ERR_ARG;
   int dform, dsplits;
   lm_pick(M, N, K, &dform, &dsplits);
