@@ -171,8 +171,8 @@ def sweep(args):
 def ktable(args):
     import sqlite3
     db = sqlite3.connect(args.db)
-    rows = db.execute("select name, duration from kernels where name like '%gemm_wf_kernel%' or name like '%gemm_fp8_kernel%' "
-                      "or name like '%gemm_w4a16_kernel%' order by start").fetchall()
+    rows = db.execute("select name, duration from kernels where name like '%gemm_wf_kernel%' or name like '%wq_gemm_kernel%' "
+                      "order by start").fetchall()
     per = (args.reps + 1) * 8
     shapes = {"qkv": (10240, 8192), "o_proj": (8192, 8192), "gate_up": (57344, 8192), "down_proj": (8192, 28672)}
     print("kind,N,K,dtype,kernel,calls,avg_us,min_us,bytes,frac_8TBs")

@@ -145,7 +145,7 @@ def step(args):
 def ktable(args):
     import sqlite3
     db = sqlite3.connect(args.db)
-    rows = db.execute("select name, duration from kernels where name like '%gemm_w4a16_kernel%' order by start").fetchall()
+    rows = db.execute("select name, duration from kernels where name like '%wq_gemm_kernel%' order by start").fetchall()
     per = (args.reps + TIME_WARMUPS) * COPIES           # dispatches of one (matrix, pass): P._time runs fn once before timing
     shapes = {kind: (N, K) for kind, (N, K, _) in P._shapes(P.MODELS["70b"]).items()}
     m8 = per * len(PASSES) * len(shapes)                # the M = 8 part of `gemm` comes first ...

@@ -1,6 +1,6 @@
 // MXFP4 weight-only GEMMs for the quantized target: y = x . W^T with bf16 activations and W = 2^(b - 127) * e2m1(q), e2m1 weight codes
-// with one e8m0 scale byte per output row and 32-column block (include/ssd_hip_mxfp4.h).  Same skeleton as gemm_w4a16_kernel
-// (gemm_w4a16.hip):
+// with one e8m0 scale byte per output row and 32-column block (include/ssd_hip_mxfp4.h).  The walk is wq_gemm_kernel's
+// (gemm_wq.h); mxfp4's own:
 //  * q is stored "mx4 frag": one 1 KiB unit per (16-row group, 128-column group), lane l holding its 8-column slices of the group's
 //    four k-tiles -- one 16-byte lane load, one contiguous 1 KiB wave load, four MFMA k-steps; the four scale bytes of the lane's row
 //    for those k-tiles are one 4-byte load.
@@ -8,10 +8,8 @@
 //    (two codes) into two bf16 already multiplied by the block scale, four conversions per 8 weights.  An MX block is one k-tile of
 //    v_mfma_f32_16x16x32_bf16, so a lane's operand slice has ONE scale; 2^e * {0, .5, 1, 1.5, 2, 3, 4, 6} is exact in bf16, so the
 //    operand is the exact weight and the MFMA goes straight into the row accumulator: no offset, no per-group partial, no scale fma.
-//  * one workgroup owns NT row groups for the whole K; its waves split K and combine through LDS in a fixed order (deterministic).
 #include "common.h"
-
-enum { MX4_ROWS = SSD_EPI_ROWS, MX4_SILU_FRAG = SSD_EPI_SILU_FRAG };
+#include "gemm_wq.h"
 
 typedef __attribute__((ext_vector_type(2))) __bf16 mx4_bf16x2_t;
 
@@ -82,16 +80,9 @@ __global__ void mx4_dequant_frag_kernel(const u32x4_t* __restrict__ q_src, const
   }
 }
 
-static int grid_for(long total) {
-  long blocks = (total + 255) / 256;
-  return (int)(blocks > 65536 ? 65536 : blocks);
-}
-
-static bool mx4_shape_ok(int N, int K) { return N > 0 && K > 0 && (N & 15) == 0 && (K & 127) == 0; }
-
 extern "C" int ssd_mx4_rows_to_frag(const void* q_rows, const void* s_rows, void* q_frag, void* s_frag, const int32_t* row_map, int N,
                                     int K, void* stream) {
-  if (!mx4_shape_ok(N, K)) return SSD_ERR_SHAPE;
+  if (!wq_shape_ok(N, K, 128)) return SSD_ERR_SHAPE;
   if (!q_rows || !s_rows || !q_frag || !s_frag) return SSD_ERR_ARG;
   const long total = (long)(N / 16) * (K / 128) * 64;
   hipLaunchKernelGGL(mx4_rows_to_frag_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)q_rows,
@@ -100,7 +91,7 @@ extern "C" int ssd_mx4_rows_to_frag(const void* q_rows, const void* s_rows, void
 }
 
 extern "C" int ssd_mx4_frag_to_rows(const void* q_frag, const void* s_frag, void* q_rows, void* s_rows, int N, int K, void* stream) {
-  if (!mx4_shape_ok(N, K)) return SSD_ERR_SHAPE;
+  if (!wq_shape_ok(N, K, 128)) return SSD_ERR_SHAPE;
   if (!q_rows || !s_rows || !q_frag || !s_frag) return SSD_ERR_ARG;
   const long total = (long)(N / 16) * (K / 128) * 64;
   hipLaunchKernelGGL(mx4_frag_to_rows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const u32x4_t*)q_frag,
@@ -109,7 +100,7 @@ extern "C" int ssd_mx4_frag_to_rows(const void* q_frag, const void* s_frag, void
 }
 
 extern "C" int ssd_mx4_dequant_frag(const void* q_frag, const void* s_frag, void* w_frag, int N, int K, void* stream) {
-  if (!mx4_shape_ok(N, K)) return SSD_ERR_SHAPE;
+  if (!wq_shape_ok(N, K, 128)) return SSD_ERR_SHAPE;
   if (!q_frag || !s_frag || !w_frag) return SSD_ERR_ARG;
   const long total = (long)(N / 16) * (K / 128) * 64;
   hipLaunchKernelGGL(mx4_dequant_frag_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const u32x4_t*)q_frag,
@@ -118,244 +109,67 @@ extern "C" int ssd_mx4_dequant_frag(const void* q_frag, const void* s_frag, void
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The GEMM.  U = column groups per stage and wave (the code bytes in flight per wave are U * NT KiB); K is dealt to the waves in
-// runs of U column groups round-robin, the < U left-over groups go to the last wave (gemm_fp8_kernel's walk).  XS: the x operands
-// ride in the double-buffered stage (MT <= 4); at MT = 8 they would not fit the VGPR budget and are loaded per group instead.
+// The GEMM: wq_gemm_kernel with a K unit of one column group (128 columns, four k-tiles) and the lane's scale quad as the stage's
+// side-band.  XS: the x operands ride in the double-buffered stage (MT <= 4); at MT = 8 they would not fit the VGPR budget and are
+// loaded per group instead.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int MT, int NT, bool XS>
-struct Mx4Stage {
-  u32x4_t a[NT];                  // 32 codes per lane: k-tiles 4c .. 4c+3
-  uint32_t s[NT];                 // the 4 scale bytes of the lane's weight row for those k-tiles
-  u32x4_t b[XS ? MT : 1][4];      // x operands of the four k-tiles
-};
-
-template <int MT, int NT, int EPI, int U, bool XS>
-__global__ void __launch_bounds__(512)
-gemm_mxfp4_kernel(const u32x4_t* __restrict__ Qf, const uint32_t* __restrict__ Sf, const u32x4_t* __restrict__ Xf,
-                  const bf16_t* __restrict__ bias, void* __restrict__ Yv, int M, int N, int K, int ldy, int tpw) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nw = blockDim.x >> 6;
-  const int KG = K >> 7, KT = K >> 5;
-  const int ntiles = (N / 16) / NT;
-  const int t_begin = blockIdx.x * tpw, t_end = min(ntiles, t_begin + tpw);
-  const u32x4_t* xp = Xf + lane;
-  const size_t wstride = (size_t)KG << 6;   // 16-byte chunks between adjacent row groups of q
-  const size_t sstride = (size_t)KG << 4;   // 4-byte scale quads between adjacent row groups of s
-  const size_t xstride = (size_t)KT << 6;   // 16-byte chunks between adjacent token tiles of x
-  const int kstep = nw * U;
-  const int kg0 = wave * U;
-  const int kmain = (KG / U) * U;
-  const u32x4_t* wp = Qf + ((size_t)t_begin * NT * wstride) + lane;
-  const uint32_t* sp = Sf + ((size_t)t_begin * NT * sstride) + (lane & 15);
-  const int mt_last = (M - 1) >> 4;
-  auto xload = [&](int mt, int kt) -> u32x4_t {
-    // token rows >= M of the last 16-row tile are padding: their lanes do not load; m-tiles past the last one re-read it
-    u32x4_t b = {0u, 0u, 0u, 0u};
-    if (NT > 1 || mt * 16 + (lane & 15) < M) b = xp[(mt < mt_last ? mt : mt_last) * xstride + ((size_t)kt << 6)];
-    return b;
+struct Mx4 {
+  static constexpr int KSHIFT = 7, KT = 4;
+  static constexpr bool ROW_SCALE = false, HAS_Z = false;
+  template <int MT, int NT>
+  struct Side {
+    uint32_t s[NT];   // the 4 scale bytes of the lane's weight row for the unit's k-tiles
   };
-  auto xgroup = [&](u32x4_t (&b)[XS ? MT : 1][4], int kg) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[mt][j] = xload(mt, 4 * kg + j);
-  };
-  auto load = [&](Mx4Stage<MT, NT, XS>(&s)[U], int kg) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        s[u].a[nt] = __builtin_nontemporal_load(wp + nt * wstride + ((size_t)(kg + u) << 6));
-        s[u].s[nt] = __builtin_nontemporal_load(sp + nt * sstride + ((size_t)(kg + u) << 4));
-      }
-      if constexpr (XS) xgroup(s[u].b, kg + u);
+  struct Band {
+    const size_t sstride;   // 4-byte scale quads between adjacent row groups of s
+    const uint32_t* sp;
+    __device__ Band(const void* Sf, const void*, size_t g0, int KG, int lane)
+        : sstride((size_t)KG << 4), sp((const uint32_t*)Sf + g0 * sstride + (lane & 15)) {}
+    template <class S>
+    __device__ void load(S& s, int nt, int kg) const {
+      s.s[nt] = __builtin_nontemporal_load(sp + nt * sstride + ((size_t)kg << 4));
     }
+    __device__ void advance(int nt) { sp += (size_t)nt * sstride; }
   };
-  Mx4Stage<MT, NT, XS> cur[U], nxt[U];
-  if (t_begin < t_end && kg0 < kmain) load(cur, kg0);
 
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int tile0 = tile * NT;
-    f32x4_t acc[NT][MT];
+  // one column group: convert each row group's four k-tile slices with their block scales, then MFMA straight into the row
+  // accumulators.  With XS the x operands come from the stage; without, each token tile's four are loaded here (from L2: x is
+  // shared by every workgroup).
+  template <int MT, int NT, bool XS, class S, class XL>
+  static __device__ __forceinline__ void group(f32x4_t (&acc)[NT][MT], const S& st, int kg, const XL& xload, const Band&) {
+    u32x4_t w[NT][4];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    // one column group: convert each row group's four k-tile slices with their block scales, then MFMA straight into the row
-    // accumulators.  With XS the x operands come from the stage; without, each token tile's four are loaded here (from L2: x is
-    // shared by every workgroup).
-    auto group = [&](const u32x4_t (&a)[NT], const uint32_t (&sc)[NT], const u32x4_t (&bs)[XS ? MT : 1][4], int kg) {
-      u32x4_t w[NT][4];
+      for (int j = 0; j < 4; ++j) w[nt][j] = mx4_to_bf16(st.a[nt][j], mx4_scale(st.s[nt], j));
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      u32x4_t b[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = XS ? st.b[XS ? mt : 0][j] : xload(mt, 4 * kg + j);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[nt][j] = mx4_to_bf16(a[nt][j], mx4_scale(sc[nt], j));
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        u32x4_t b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = XS ? bs[XS ? mt : 0][j] : xload(mt, 4 * kg + j);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[nt][mt] = mfma16(w[nt][j], b[j], acc[nt][mt]);
-      }
-    };
-    auto compute = [&](Mx4Stage<MT, NT, XS>(&s)[U], int kg) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) group(s[u].a, s[u].s, s[u].b, kg + u);
-    };
-
-    int kg = kg0;
-    if (kg < kmain) {
-      for (; kg + kstep < kmain; kg += kstep) {
-        load(nxt, kg + kstep);
-        compute(cur, kg);
-#pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-      }
-      compute(cur, kg);
+        for (int j = 0; j < 4; ++j) acc[nt][mt] = mfma16(w[nt][j], b[j], acc[nt][mt]);
     }
-    for (kg = (wave == nw - 1) ? kmain : KG; kg < KG; ++kg) {   // K remainder (< U groups): last wave
-      u32x4_t a[NT], b[XS ? MT : 1][4];
-      uint32_t sc[NT];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        a[nt] = __builtin_nontemporal_load(wp + nt * wstride + ((size_t)kg << 6));
-        sc[nt] = __builtin_nontemporal_load(sp + nt * sstride + ((size_t)kg << 4));
-      }
-      if constexpr (XS) xgroup(b, kg);
-      group(a, sc, b, kg);
-    }
-
-    // next tile: advance the weight pointers and put its first loads in flight before the combine
-    wp += (size_t)NT * wstride;
-    sp += (size_t)NT * sstride;
-    if (tile + 1 < t_end && kg0 < kmain) load(cur, kg0);
-
-    // ---- cross-wave split-K combine through LDS, fixed order ----
-    f32x4_t* red = reinterpret_cast<f32x4_t*>(smem);  // [nw][NT*MT][64]
-    constexpr int ITEMS = NT * MT;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) red[((wave * ITEMS) + nt * MT + mt) * 64 + lane] = acc[nt][mt];
-    __syncthreads();
-
-    const int mcol = lane & 15;        // D column j -> token row m
-    const int nrow = (lane >> 4) * 4;  // D rows nrow + r -> output feature n
-    if (EPI == MX4_SILU_FRAG) {
-      constexpr int PAIRS = NT / 2;
-      const int KT2 = (N >> 1) >> 5;
-      u32x2_t* out = reinterpret_cast<u32x2_t*>(Yv);
-      for (int item = wave; item < PAIRS * MT; item += nw) {
-        const int pr = item / MT, mt = item % MT;
-        f32x4_t g = f32x4_t{0.f, 0.f, 0.f, 0.f}, u = g;
-        for (int w = 0; w < nw; ++w) {
-          g += red[((w * ITEMS) + (2 * pr) * MT + mt) * 64 + lane];
-          u += red[((w * ITEMS) + (2 * pr + 1) * MT + mt) * 64 + lane];
-        }
-        const int m = mt * 16 + mcol;
-        const int ng = (tile0 + 2 * pr) * 16 + nrow, nu = (tile0 + 2 * pr + 1) * 16 + nrow;   // packed rows of gate / up
-        const int n = ((tile0 >> 1) + pr) * 16 + nrow;                                       // feature index in [0, N/2)
-        float o[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float gb = g[r], ub = u[r];
-          if (bias) { gb += bf2f(bias[ng + r]); ub += bf2f(bias[nu + r]); }
-          gb = round_bf(gb); ub = round_bf(ub);
-          o[r] = (gb / (1.0f + __expf(-gb))) * ub;
-        }
-        if (m < M) out[frag_chunk(m, n >> 3, KT2) * 2 + ((n >> 2) & 1)] = u32x2_t{pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
-      }
-    } else {
-      for (int item = wave; item < ITEMS; item += nw) {
-        const int nt = item / MT, mt = item % MT;
-        f32x4_t s = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        for (int w = 0; w < nw; ++w) s += red[((w * ITEMS) + item) * 64 + lane];
-        const int m = mt * 16 + mcol;
-        const int n = (tile0 + nt) * 16 + nrow;
-        if (bias) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) s[r] += bf2f(bias[n + r]);
-        }
-        if (m < M)
-          *reinterpret_cast<u32x2_t*>(reinterpret_cast<bf16_t*>(Yv) + (size_t)m * ldy + n) = u32x2_t{pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3])};
-      }
-    }
-    __syncthreads();   // the combine area is reused by the next tile
   }
-}
 
-template <int MT, int NT, int EPI, int U, bool XS>
-static int mx4_launch(const void* x, const void* q, const void* s, const void* bias, void* y, int M, int N, int K, int ldy, int waves,
-                      int tpw, hipStream_t st) {
-  const int ntiles = (N / 16) / NT;
-  if (tpw < 1) tpw = 1;
-  const int blocks = (ntiles + tpw - 1) / tpw;
-  const size_t lds = (size_t)waves * NT * MT * 64 * sizeof(f32x4_t);
-  if (lds > 64 * 1024) return SSD_ERR_ARG;
-  hipLaunchKernelGGL((gemm_mxfp4_kernel<MT, NT, EPI, U, XS>), dim3(blocks), dim3(waves * 64), lds, st, (const u32x4_t*)q,
-                     (const uint32_t*)s, (const u32x4_t*)x, (const bf16_t*)bias, y, M, N, K, ldy, tpw);
-  return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
-}
-
-// U per (MT, NT, deep): as gemm_w4a16.hip -- 2-4 KiB of codes in flight per wave in the plain form (x staged with them), twice that
-// in the deep one (x loaded per group), within the VGPR budget of a <= 8-wave workgroup without spills (the double-buffered stage is
-// 2 U (5 NT + 16 MT) VGPRs with x in it, 10 U NT without)
-template <int MT, int EPI>
-static int mx4_dispatch_nt(const void* x, const void* q, const void* s, const void* bias, void* y, int M, int N, int K, int ldy, int nt,
-                           bool deep, int waves, int tpw, hipStream_t st) {
-#define MX4L(NTV, UV, XSV) return mx4_launch<MT, NTV, EPI, UV, XSV>(x, q, s, bias, y, M, N, K, ldy, waves, tpw, st)
-  if constexpr (MT == 1) {
-    if (nt == 1) { if constexpr (EPI == MX4_SILU_FRAG) return SSD_ERR_ARG; else { if (deep) MX4L(1, 8, false); MX4L(1, 2, true); } }
-    if (nt == 2) { if (deep) MX4L(2, 4, false); MX4L(2, 1, true); }
-    if (nt == 4) { if (deep) MX4L(4, 2, false); MX4L(4, 1, true); }
-  } else if constexpr (MT == 2) {
-    if (deep) return SSD_ERR_ARG;
-    if (nt == 1) { if constexpr (EPI == MX4_SILU_FRAG) return SSD_ERR_ARG; else MX4L(1, 2, true); }
-    if (nt == 2) MX4L(2, 1, true);
-  } else if constexpr (MT == 4) {
-    if (deep) return SSD_ERR_ARG;
-    if (nt == 1) { if constexpr (EPI == MX4_SILU_FRAG) return SSD_ERR_ARG; else MX4L(1, 1, true); }
-    if (nt == 2) MX4L(2, 1, true);
-  } else {
-    if (deep) return SSD_ERR_ARG;
-    if (nt == 1) { if constexpr (EPI == MX4_SILU_FRAG) return SSD_ERR_ARG; else MX4L(1, 1, false); }
-    if (nt == 2) MX4L(2, 1, false);
-  }
-#undef MX4L
-  return SSD_ERR_ARG;
-}
+  // U per (MT, NT, deep): as gemm_w4a16.hip -- 2-4 KiB of codes in flight per wave in the plain form (x staged with them), twice that
+  // in the deep one (x loaded per group), within the VGPR budget of a <= 8-wave workgroup without spills (the double-buffered stage is
+  // 2 U (5 NT + 16 MT) VGPRs with x in it, 10 U NT without)
+  static constexpr WqForm FORMS[4][3][2] = {
+      /* MT 1 */ {{{2, true}, {8, false}}, {{1, true}, {4, false}}, {{1, true}, {2, false}}},
+      /* MT 2 */ {{{2, true}, {}}, {{1, true}, {}}, {}},
+      /* MT 4 */ {{{1, true}, {}}, {{1, true}, {}}, {}},
+      /* MT 8 */ {{{1, false}, {}}, {{1, false}, {}}, {}},
+  };
+};
 
 extern "C" int ssd_gemm_mxfp4_cfg(const void* x_frag, const void* q_frag, const void* s_frag, const void* bias, void* y, int M, int N,
                                   int K, int ldy, int epilogue, int nt, int waves, void* stream) {
-  if (M <= 0 || M > 128 || !mx4_shape_ok(N, K)) return SSD_ERR_SHAPE;
-  if (!x_frag || !q_frag || !s_frag || !y) return SSD_ERR_ARG;
-  if (epilogue == MX4_ROWS && ldy < N) return SSD_ERR_SHAPE;
-  const int tpw = (waves >> 8) & 0xff;
-  const bool deep = (nt >> 8) & 1;
-  waves &= 0xff;
-  nt &= 0xff;
-  if (waves < 1 || waves > 8 || (nt != 1 && nt != 2 && nt != 4) || ((N / 16) % nt) != 0) return SSD_ERR_ARG;
-  if (epilogue == MX4_SILU_FRAG && ((nt & 1) || (N & 63))) return SSD_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int mt = (M + 15) / 16;
-#define MX4_MT(MTV)                                                                                                                      \
-  switch (epilogue) {                                                                                                                    \
-    case MX4_ROWS: return mx4_dispatch_nt<MTV, MX4_ROWS>(x_frag, q_frag, s_frag, bias, y, M, N, K, ldy, nt, deep, waves, tpw, st);        \
-    case MX4_SILU_FRAG: return mx4_dispatch_nt<MTV, MX4_SILU_FRAG>(x_frag, q_frag, s_frag, bias, y, M, N, K, ldy, nt, deep, waves, tpw, st); \
-    default: return SSD_ERR_ARG;                                                                                                         \
-  }
-  if (mt == 1) { MX4_MT(1) }
-  if (mt == 2) { MX4_MT(2) }
-  if (mt <= 4) { MX4_MT(4) }
-  { MX4_MT(8) }
-#undef MX4_MT
+  return wq_gemm_cfg<Mx4>(WqArgs{x_frag, q_frag, s_frag, nullptr, bias, y, M, N, K, ldy}, epilogue, nt, waves, stream);
 }
+
 
 // Default decomposition.  One token tile: the classes of ssd_gemm_w4a16 (same unit size, same bytes per row group within 3 %), checked
 // against the M = 8 sweep of every explicit decomposition at the 1B / 8B / 70B / Qwen3-32B shapes (profiles/mxfp4_sweep.jsonl):
@@ -367,9 +181,9 @@ extern "C" int ssd_gemm_mxfp4_cfg(const void* x_frag, const void* q_frag, const 
 // combine <= 64 KiB.
 extern "C" int ssd_gemm_mxfp4(const void* x_frag, const void* q_frag, const void* s_frag, const void* bias, void* y, int M, int N, int K,
                               int ldy, int epilogue, void* stream) {
-  if (M <= 0 || M > 128 || !mx4_shape_ok(N, K)) return SSD_ERR_SHAPE;
+  if (M <= 0 || M > 128 || !wq_shape_ok(N, K, 128)) return SSD_ERR_SHAPE;
   const int groups = N / 16, KG = K / 128, mt = (M + 15) / 16;
-  const bool silu = epilogue == MX4_SILU_FRAG;
+  const bool silu = epilogue == WQ_SILU_FRAG;
   int nt, waves;
   if (mt == 1) {
     if (silu) {

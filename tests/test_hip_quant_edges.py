@@ -1,7 +1,8 @@
 """The three weight-only GEMM families (csrc/gemm_fp8.hip, gemm_w4a16.hip, gemm_mxfp4.hip) at the edges their per-format test files do
-not visit.  The three kernels are hand-copied versions of one walk -- K dealt to the waves in runs of U units with a remainder loop
-on the last wave, a token-tile clamp, a next-tile prefetch with a pointer advance, an LDS split-K combine, two epilogues -- so one
-harness drives all three through a small per-format adapter:
+not visit.  The three families are instantiations of one kernel skeleton (wq_gemm_kernel, csrc/gemm_wq.h: K dealt to the waves in
+runs of U units with a remainder loop on the last wave, a token-tile clamp, a next-tile prefetch with a pointer advance, an LDS
+split-K combine, two epilogues) with a per-format policy struct for the K unit, the side-band and the conversion -- so one harness
+drives all three through a small per-format adapter:
 
   * K unit counts that are not a multiple of U, smaller than U, and smaller than waves * U (idle waves in the combine);
   * every M around the 16-row tile boundaries, so every token-tile template runs with tiles past the last one and a ragged last tile;
@@ -33,7 +34,8 @@ BF = torch.bfloat16
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Per-format adapters.  `kernels` restates *_dispatch_nt: (token-tile template, nt, deep) -> (U, x staged with the codes).
+# Per-format adapters.  `kernels` restates each policy's FORMS table (Fp8::FORMS, W4<ZP>::FORMS, Mx4::FORMS in the three .hip files):
+# (token-tile template, nt, deep) -> (U, x staged with the codes).
 # ---------------------------------------------------------------------------------------------------------------------
 _W4_KERNELS = {
     (1, 1, False): (2, True), (1, 1, True): (8, False), (1, 2, False): (1, True), (1, 2, True): (4, False),
@@ -153,7 +155,7 @@ def mtr(M: int) -> int:
 
 
 def valid(fmt, M, N, K, epilogue, nt, deep, waves) -> bool:
-    """The rules of the headers and of *_cfg / *_dispatch_nt / *_launch."""
+    """The rules of the headers and of wq_gemm_cfg / the FORMS tables / wq_launch (csrc/gemm_wq.h)."""
     if not 1 <= M <= 128 or N <= 0 or N % 16 or K <= 0 or K % fmt.kunit:
         return False
     if not 1 <= waves <= 8 or nt not in (1, 2, 4) or (N // 16) % nt:

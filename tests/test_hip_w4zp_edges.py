@@ -1,7 +1,7 @@
 """The zero-point W4A16 GEMM (csrc/gemm_w4a16.hip, ZP instantiations) at the edges of tests/test_hip_quant_edges.py: that file's case
 table, harness, bars and test bodies, imported and run through one more per-format adapter -- K remainders and idle waves, every M
 around the tile borders, ragged tiles per workgroup, sentinel-guarded outputs, poisoned x padding, SILU_FRAG + bias, the _cfg
-refusals -- for every zero-point instantiation (`kernels` below restates w4_dispatch_nt for ZP = true)."""
+refusals -- for every zero-point instantiation (`kernels` below restates W4<true>::FORMS)."""
 from __future__ import annotations
 
 import pytest
