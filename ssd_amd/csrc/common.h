@@ -18,6 +18,7 @@ constexpr int SSD_MAX_DEVICES = 16;  // per-device host-side caches (function at
 #include "ssd_hip.h"
 #include "ssd_hip_tune.h"
 #include "ssd_hip_quant.h"
+#include "ssd_hip_fp8b.h"
 #include "ssd_hip_w4a16.h"
 #include "ssd_hip_w4zp.h"
 #include "ssd_hip_mxfp4.h"

@@ -7,16 +7,7 @@
 //  * the row scale (and the bias) are applied to the fp32 sums in the epilogue.
 #include "common.h"
 #include "gemm_wq.h"
-
-// 8 e4m3 codes (two 32-bit words) -> the 8 bf16 of one MFMA operand slice
-__device__ __forceinline__ u32x4_t fp8x8_to_bf16(uint32_t w0, uint32_t w1) {
-  u32x4_t r;
-  r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false));
-  r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true));
-  r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false));
-  r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true));
-  return r;
-}
+#include "gemm_fp8.h"   // fp8x8_to_bf16, shared with gemm_fp8b.hip
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Layout: row-major codes -> fp8 frag (with an optional destination -> source row map), and back.

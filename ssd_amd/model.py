@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from ssd_amd.hip import ops as H
 from ssd_amd.hip import quant_ops as Q
+from ssd_amd.hip import fp8b_ops as F8B
 from ssd_amd.hip import w4_ops as W4
 from ssd_amd.hip import w4zp_ops as W4Z
 from ssd_amd.hip import mx4_ops as MX4
@@ -269,13 +270,18 @@ class HipDecoder:
         layout (gate_up with gate/up row groups interleaved for the fused SiLU epilogue).  A decoder linear may also come as
         (name, (q float8_e4m3fn [N, K], s fp32 [N])) from a pre-quantized checkpoint.  An fp8 decoder quantizes each bf16 linear
         as it arrives (never the whole model in both forms) and stores "<name>" = fp8 frag codes, "<name>_scale" = fp32 [N] in
-        the packed row order.  Likewise a w4a16 decoder takes bf16 linears or quant.W4Tensor(packed, scale) from a pack-quantized
+        the packed row order; a block-scaled quant.FP8BTensor(codes, rowscale) keeps its codes and stores "<name>_bscale" = fp32
+        [N / 16, ceil(K / 128)] instead (include/ssd_hip_fp8b.h), linear by linear.  Likewise a w4a16 decoder takes bf16 linears or quant.W4Tensor(packed, scale) from a pack-quantized
         checkpoint and stores "<name>" = w4 frag codes, "<name>_scale" = bf16 w4 frag scales (include/ssd_hip_w4a16.h).  An mxfp4
         decoder takes bf16 linears or quant.MX4Tensor(packed, scale) and stores "<name>" = mx4 frag codes, "<name>_scale" = mx4 frag
         scale bytes (include/ssd_hip_mxfp4.h).  A w4a16 decoder also takes quant.W4ZTensor(packed, scale, zero) and then stores
         "<name>_zero" = the zero-point table (include/ssd_hip_w4zp.h) next to the other two.  A bf16 decoder computes with the exact
         dequantized matrix of whatever it is handed; a quantized decoder refuses tensors of another format."""
         for name, w in weight_iter:
+            if isinstance(w, quant.FP8BTensor) and not (self.fp8 and quant.is_quantized_linear(name)):
+                if self.quantized and quant.is_quantized_linear(name):
+                    raise ValueError(f"{name}: block-scaled fp8 tensors cannot load into {'a w4a16' if self.w4 else 'an mxfp4'} decoder")
+                w = quant.dequantize_fp8_block(w.codes.to(self.device), w.rowscale.to(self.device))
             if isinstance(w, quant.W4ZTensor) and not self.w4:
                 if self.quantized:
                     raise ValueError(f"{name}: zero-point int4 tensors cannot load into {'an fp8' if self.fp8 else 'an mxfp4'} decoder")
@@ -329,6 +335,16 @@ class HipDecoder:
         return None
 
     def _load_fp8(self, name: str, w) -> None:
+        if isinstance(w, quant.FP8BTensor):     # block-scaled: the codes as below, the scales as a group table under "<name>_bscale"
+            q, rs = w.codes.to(self.device).contiguous(), w.rowscale.to(self.device).to(torch.float32).contiguous()
+            N, K = q.shape
+            assert q.dtype == quant.FP8 and tuple(rs.shape) == (N, -(-K // quant.FP8_BLOCK)), (name, q.dtype, rs.shape)
+            row_map = self._row_map(name, N)
+            out = torch.empty(N * K, dtype=torch.uint8, device=self.device)
+            Q.fp8_rows_to_frag(q.view(torch.uint8), out, N, K, row_map=row_map)
+            self.w[name] = out
+            self.w[name + "_bscale"] = quant.fp8_block_group_scales(rs, row_map, name)
+            return
         q, s = (w[0].to(self.device), w[1].to(self.device)) if isinstance(w, tuple) else quant.quantize_fp8(w.to(self.device))
         q, s = q.contiguous(), s.to(torch.float32).reshape(-1).contiguous()
         N, K = q.shape
@@ -499,8 +515,15 @@ class HipDecoder:
         H.gemm_pf(xf, w, None, T, N, K, N, self._ws_pf, epilogue=H.PF_EPI_PARTIALS)
         return Slabs(self._ws_pf, S, T)
 
-    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None, zero=None):
-        if scale is not None and self.w4 and zero is not None:   # w4a16 codes (w) + group scales + group zero points
+    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None, zero=None, bscale=None):
+        if bscale is not None:          # fp8 codes (w) + block scales per 16-row group (a linear has these or row scales, never both)
+            assert scale is None and self.fp8
+            if T <= self.FP8_DIRECT_MAX_T:
+                F8B.gemm_fp8b(xf, w, bscale, y, T, N, K, ldy, epi, bias)
+                return
+            F8B.fp8b_dequant_frag(w, bscale, self._deq, N, K)
+            w = self._deq
+        elif scale is not None and self.w4 and zero is not None:   # w4a16 codes (w) + group scales + group zero points
             if T <= self.W4_DIRECT_MAX_T:
                 W4Z.gemm_w4a16_zp(xf, w, scale, zero, y, T, N, K, ldy, epi, bias)
                 return
@@ -774,7 +797,7 @@ class HipDecoder:
                                       self.hd, self.block_size, **head_norm)
                 return
         self._gemm(xf, self.h, wq, self.qkv_n, self.buf_qkv, T, self.qkv_n, bias=bias, scale=w.get(p + "self_attn.qkv_proj.weight_scale"),
-                   zero=w.get(p + "self_attn.qkv_proj.weight_zero"))
+                   zero=w.get(p + "self_attn.qkv_proj.weight_zero"), bscale=w.get(p + "self_attn.qkv_proj.weight_bscale"))
         if gemm_only:
             return
         if self.kv8:
@@ -798,7 +821,8 @@ class HipDecoder:
             S, wv = self._parts(which, T)
             H.gemm_parts(xf, w, T, self.h, K, parts=slabs, splits=S, waves=wv)
             return Slabs(slabs, S, T)
-        self._gemm(xf, K, w, self.h, self.buf_h, T, self.h, scale=self.w.get(name + "_scale"), zero=self.w.get(name + "_zero"))
+        self._gemm(xf, K, w, self.h, self.buf_h, T, self.h, scale=self.w.get(name + "_scale"), zero=self.w.get(name + "_zero"),
+                   bscale=self.w.get(name + "_bscale"))
         return None
 
     def launch_o(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> Slabs | None:
@@ -818,7 +842,8 @@ class HipDecoder:
         if not gemm_only:
             self._add_norm(src, T, w[p + "post_attention_layernorm.weight"], res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
         self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG,
-                   scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"))
+                   scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"),
+                   bscale=w.get(p + "mlp.gate_up_proj.weight_bscale"))
 
     def launch_down(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> Slabs | None:
         return self._launch_to_h("d", li, T, parts, pf_partials)

@@ -62,6 +62,78 @@ def qkv_row_map(nh: int, nkv: int, hd: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Block-scaled FP8 (include/ssd_hip_fp8b.h): e4m3fn codes with one fp32 scale per block of FP8_BLOCK rows and FP8_BLOCK columns,
+# W = s[n // 128, k // 128] * q[n, k]: the form of `quant_method: "fp8"` checkpoints with weight_block_size [128, 128] (their
+# weight_scale_inv tensor is s).  Grids are ceil: the last block row / column may be ragged.  The quantizer, fp32 on the tensor's
+# device, per block:
+#
+#     amax = max |w| over the block
+#     s = amax / 448,  inv = 448 / amax               (an all-zero block gets s = 1, q = 0)
+#     q = e4m3fn(clamp(fp32(w) * inv, -448, 448))     (round to nearest even, saturating)
+#
+# On the host a linear carries its scales expanded to one ROW of block scales per output row, [N, ceil(K / 128)]: that form
+# survives torch.cat of q | k | v and gate | up (whose sources have their own block grids) and any row permutation.  The device
+# keeps one scale per 16-row group of the packed order and column block (fp8_block_group_scales).
+# ---------------------------------------------------------------------------------------------------------------------
+FP8_BLOCK = 128
+
+
+class FP8BTensor(NamedTuple):
+    """A block-scaled FP8 decoder linear on the host: codes float8_e4m3fn [N, K], rowscale fp32 [N, ceil(K / 128)] (row n holds
+    the scales of the block row its source tensor put row n in)."""
+    codes: torch.Tensor
+    rowscale: torch.Tensor
+
+
+def expand_fp8_block_scales(s: torch.Tensor, N: int) -> torch.Tensor:
+    """Block scales [ceil(N / 128), KB] -> one row of scales per output row, fp32 [N, KB]."""
+    assert s.dim() == 2 and s.shape[0] == -(-N // FP8_BLOCK), (tuple(s.shape), N)
+    return s.float().repeat_interleave(FP8_BLOCK, dim=0)[:N].contiguous()
+
+
+def _fp8_block_elem_scales(rowscale: torch.Tensor, K: int) -> torch.Tensor:
+    return rowscale.float().repeat_interleave(FP8_BLOCK, dim=1)[:, :K]
+
+
+def quantize_fp8_block(w: torch.Tensor) -> FP8BTensor:
+    """[N, K] bf16 -> FP8BTensor(codes [N, K], rowscale [N, ceil(K / 128)]), on w's device (ragged last blocks allowed)."""
+    N, K = w.shape
+    NB, KB = -(-N // FP8_BLOCK), -(-K // FP8_BLOCK)
+    wf = w.float()
+    pad = torch.zeros(NB * FP8_BLOCK, KB * FP8_BLOCK, dtype=torch.float32, device=w.device)
+    pad[:N, :K] = wf.abs()
+    amax = pad.reshape(NB, FP8_BLOCK, KB, FP8_BLOCK).amax(dim=(1, 3))
+    amax = torch.where(amax == 0, torch.full_like(amax, FP8_MAX), amax)
+    inv = _fp8_block_elem_scales(expand_fp8_block_scales(FP8_MAX / amax, N), K)
+    q = (wf * inv).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+    return FP8BTensor(q, expand_fp8_block_scales(amax / FP8_MAX, N))
+
+
+def dequantize_fp8_block(codes: torch.Tensor, rowscale: torch.Tensor) -> torch.Tensor:
+    """bf16(s * q), the product in fp32: the weights a block-scaled fp8 target computes with, as a bf16 matrix."""
+    return (codes.float() * _fp8_block_elem_scales(rowscale, codes.shape[1])).to(torch.bfloat16)
+
+
+def fp8_block_group_scales(rowscale: torch.Tensor, row_map: torch.Tensor | None, name: str = "") -> torch.Tensor:
+    """rowscale fp32 [N, KB] in source row order -> the device table fp32 [N / 16, KB]: one scale per 16-row group of the PACKED row
+    order (row_map names the source row of every packed row; None = in order) and column block.  Raises ValueError if the rows of
+    some packed group do not share their scales (the shipped row maps keep every group inside one 128-row block for head_dim 64
+    and 128; head_dim 256 would not)."""
+    N, KB = rowscale.shape
+    assert N % 16 == 0, N
+    s = rowscale.float()
+    if row_map is not None:
+        s = s[row_map.to(s.device).long()]
+    g = s.reshape(N // 16, 16, KB)
+    mixed = (g != g[:, :1]).any(dim=2).any(dim=1)
+    if bool(mixed.any()):
+        bad = int(mixed.nonzero()[0])
+        raise ValueError(f"{name or 'linear'}: packed rows {16 * bad}..{16 * bad + 15} draw from source rows with different block scales; "
+                         "the block-scaled fp8 GEMM needs one scale per 16-row group")
+    return g[:, 0].contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # W4A16: signed int4 codes q in [-8, 7] with one bf16 scale per output row and 128-column group, W ~= s[n, k // 128] * q[n, k]
 # (csrc/gemm_w4a16.hip).  Round to nearest, fp32 on the tensor's device:
 #

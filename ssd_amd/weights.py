@@ -417,11 +417,44 @@ def int4_checkpoint_scheme(qc: dict | None) -> dict | None:
     return {"method": GPTQ_METHOD, "zero_offset": GPTQ_ZERO_OFFSET[str(fmt).lower()]}
 
 
+# Block-scaled FP8 checkpoints (the Qwen3-*-FP8 / DeepSeek-style exports): the config field names and the tensor suffix, kept in
+# one place.  They are written from memory of the format and have not been checked against a published checkpoint (DESIGN.md,
+# "Block-scaled FP8 checkpoints"): quantization_config = {"quant_method": "fp8", "fmt": "e4m3", "weight_block_size": [128, 128],
+# "activation_scheme": "dynamic"}, every quantized linear X stored as X.weight (float8_e4m3fn [N, K]) and X.weight_scale_inv
+# ([ceil(N / 128), ceil(K / 128)], W = weight_scale_inv[n // 128, k // 128] * code[n, k]); linears listed under
+# modules_to_not_convert / ignored_layers are stored as plain bf16 .weight tensors (the tensor's dtype decides here, not the list).
+FP8_BLOCK_METHOD = "fp8"
+FP8_BLOCK_SIZE_FIELD, FP8_BLOCK_FMT_FIELD, FP8_BLOCK_FMTS = "weight_block_size", "fmt", (None, "e4m3")
+FP8_BLOCK_ACTIVATION_FIELD = "activation_scheme"        # read and ignored: activations stay bf16
+FP8_BLOCK_SKIP_FIELDS = ("modules_to_not_convert", "ignored_layers")
+FP8_BLOCK_SCALE_SUFFIX = "_scale_inv"                   # appended to "<linear>.weight"
+
+
+def fp8_block_scheme(qc: dict | None) -> bool:
+    """True for the block-scaled fp8 scheme an fp8 target runs (quant_method "fp8" without compressed-tensors config_groups, e4m3
+    codes, 128 x 128 blocks), False for any other quantization_config; other block sizes, fmt e5m2 and a missing block size
+    (AutoFP8-style per-tensor checkpoints) are refused here by name."""
+    if not qc or qc.get("quant_method") != FP8_BLOCK_METHOD or "config_groups" in qc:
+        return False
+    fmt = qc.get(FP8_BLOCK_FMT_FIELD)
+    if (fmt.lower() if isinstance(fmt, str) else fmt) not in FP8_BLOCK_FMTS:
+        raise ValueError(f"unsupported fp8 {FP8_BLOCK_FMT_FIELD} {fmt!r}: only e4m3 (OCP float8_e4m3fn) codes can be loaded")
+    bs = qc.get(FP8_BLOCK_SIZE_FIELD)
+    if bs is None:
+        raise ValueError(f"unsupported fp8 checkpoint without {FP8_BLOCK_SIZE_FIELD}: per-tensor (AutoFP8-style) quant_method 'fp8' "
+                         "checkpoints are not supported, only 128 x 128 block scales")
+    from ssd_amd.quant import FP8_BLOCK
+    if list(bs) != [FP8_BLOCK, FP8_BLOCK]:
+        raise ValueError(f"unsupported fp8 {FP8_BLOCK_SIZE_FIELD} {bs!r}: only [{FP8_BLOCK}, {FP8_BLOCK}]")
+    qc.get(FP8_BLOCK_ACTIVATION_FIELD)      # "dynamic" or "static": activations stay bf16 either way
+    return True
+
+
 def checkpoint_quantization(model_dir: str) -> str | None:
-    """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales, "w4a16" for a
-    pack-quantized one with symmetric int4 weights in groups of 128 columns and for an AutoAWQ / GPTQ one (int4_checkpoint_scheme),
-    "mxfp4" for an MXFP4 one (config.json quantization_config), None for an unquantized one; every other quantization format is
-    refused here, before any tensor is read."""
+    """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales and for a block-scaled
+    fp8 one (fp8_block_scheme), "w4a16" for a pack-quantized one with symmetric int4 weights in groups of 128 columns and for an
+    AutoAWQ / GPTQ one (int4_checkpoint_scheme), "mxfp4" for an MXFP4 one (config.json quantization_config), None for an
+    unquantized one; every other quantization format is refused here, before any tensor is read."""
     return _checkpoint_kind(_quantization_config(model_dir))
 
 
@@ -432,10 +465,13 @@ def _checkpoint_kind(qc: dict | None) -> str | None:
     method = qc.get("quant_method")
     if int4_checkpoint_scheme(qc) is not None:
         return "w4a16"
+    if fp8_block_scheme(qc):
+        return "fp8"
     if method != "compressed-tensors":
         raise ValueError(f"unsupported quantization_config.quant_method {method!r}: only compressed-tensors float8 checkpoints "
-                         "(per-channel or per-tensor weight scales), pack-quantized int4 ones (group 128), MXFP4 ones, and AutoAWQ / "
-                         "GPTQ int4 ones (group 128) can be loaded")
+                         "(per-channel or per-tensor weight scales), pack-quantized int4 ones (group 128), MXFP4 ones, AutoAWQ / "
+                         "GPTQ int4 ones (group 128), and block-scaled fp8 ones (quant_method 'fp8', weight_block_size [128, 128]) can "
+                         "be loaded")
     groups = qc.get("config_groups") or {}
     if not groups:
         raise ValueError("compressed-tensors checkpoint without config_groups")
@@ -608,9 +644,13 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
     ``mxfp4`` (codes and scale bytes bit for bit; scale bytes outside 2..252 are refused) and as the exact bf16 matrix
     2^(b - 127) * e2m1(q), sharded as usual, otherwise.  MXFP4 checkpoints into fp8 / w4a16 targets and the reverse are refused.
     From an AutoAWQ or GPTQ int4 checkpoint (_load_awq_gptq), a quantized linear comes as quant.W4ZTensor(packed, scale, zero) when
-    ``w4a16`` (a plain W4Tensor when all its zero points are 8) and as bf16(s * (u - z)) otherwise; fp8 and mxfp4 targets refuse it."""
+    ``w4a16`` (a plain W4Tensor when all its zero points are 8) and as bf16(s * (u - z)) otherwise; fp8 and mxfp4 targets refuse it.
+    From a block-scaled fp8 checkpoint (fp8_block_scheme), a quantized linear comes as quant.FP8BTensor(codes, rowscale fp32
+    [N, ceil(K / 128)]) when ``fp8`` (codes bit for bit; every source tensor's weight_scale_inv expanded to one row of block scales
+    per output row, then concatenated) and as bf16(s * q), sharded as usual, otherwise; w4a16 and mxfp4 targets refuse it."""
     from safetensors import safe_open
     from ssd_amd.quant import FP8, dequantize_fp8, W4Tensor, dequantize_w4a16, MX4Tensor, dequantize_mxfp4, check_mxfp4_scales
+    from ssd_amd.quant import FP8_BLOCK, FP8BTensor, dequantize_fp8_block, expand_fp8_block_scales
     assert fp8 + w4a16 + mxfp4 <= 1
     qc = _quantization_config(model_dir)
     kind = _checkpoint_kind(qc)
@@ -623,6 +663,7 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         yield from _load_awq_gptq(cfg, model_dir, scheme, rank, tp, out_device, w4a16)
         return
     ckpt_fp8 = kind == "fp8"
+    block = fp8_block_scheme(qc)
     if kind == "mxfp4" and (fp8 or w4a16):
         raise ValueError(f"an mxfp4 checkpoint cannot load into {'an fp8' if fp8 else 'a w4a16'} target: use quantization='mxfp4' or None")
     if kind in ("fp8", "w4a16") and mxfp4:
@@ -637,7 +678,7 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         with safe_open(f, "pt", "cpu") as sf:
             for k in sf.keys():
                 index[k] = f
-    if any(k.endswith("weight_scale_inv") for k in index):
+    if not block and any(k.endswith("weight_scale_inv") for k in index):
         raise ValueError("block-scaled fp8 checkpoints (weight_scale_inv) are not supported: use per-channel or per-tensor scales")
     assert not (fp8 and tp > 1), "fp8 targets are single-rank"
     assert not (w4a16 and tp > 1), "w4a16 targets are single-rank"
@@ -686,6 +727,29 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         check_mxfp4_scales(base + MXFP4_SCALE_SUFFIX, s)
         return MX4Tensor(packed.contiguous(), s.contiguous())
 
+    def get_fp8_block(name: str, q: torch.Tensor) -> FP8BTensor:
+        sname = name + FP8_BLOCK_SCALE_SUFFIX
+        if sname not in index:
+            raise ValueError(f"{name} is float8_e4m3fn but the checkpoint has no {sname}")
+        s = raw(sname)
+        N, K = q.shape
+        grid = (-(-N // FP8_BLOCK), -(-K // FP8_BLOCK))
+        if s.dtype not in (BF16, torch.float16, torch.float32):
+            raise ValueError(f"{sname} is {s.dtype}: expected fp32, bf16 or fp16")
+        if tuple(s.shape) != grid:
+            raise ValueError(f"{sname} has shape {tuple(s.shape)}: expected {list(grid)} ({FP8_BLOCK} x {FP8_BLOCK} blocks of a "
+                             f"[{N}, {K}] matrix)")
+        s = s.float()
+        if not bool(torch.isfinite(s).all()) or not bool((s > 0).all()):
+            raise ValueError(f"{sname} holds a scale that is not finite or not positive")
+        return FP8BTensor(q.contiguous(), expand_fp8_block_scales(s, N))
+
+    def deq(p):
+        """bf16(s * q) of a pre-quantized fp8 part, per-row or block-scaled; anything else as it is."""
+        if isinstance(p, FP8BTensor):
+            return dequantize_fp8_block(*p)
+        return dequantize_fp8(*p) if isinstance(p, tuple) else p
+
     def get(name: str):
         if name not in index and name.endswith(".weight") and name[:-len(".weight")] + ".weight_packed" in index:
             return get_mx4(name) if kind == "mxfp4" else get_w4(name)
@@ -693,6 +757,8 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         if t.dtype == FP8:
             if not ckpt_fp8:
                 raise ValueError(f"{name} is float8_e4m3fn but config.json declares no compressed-tensors quantization")
+            if block:
+                return get_fp8_block(name, t)
             s = raw(name + "_scale").float()
             N = t.shape[0]
             if s.numel() == 1:
@@ -731,16 +797,21 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
                 continue
         elif any(isinstance(p, W4Tensor) for p in parts):
             w = torch.cat([dequantize_w4a16(*p) if isinstance(p, W4Tensor) else p for p in parts], dim=0)
-        elif all(isinstance(p, tuple) for p in parts):
+        elif all(isinstance(p, FP8BTensor) for p in parts):
+            w = FP8BTensor(torch.cat([p.codes for p in parts], dim=0), torch.cat([p.rowscale for p in parts], dim=0))
+        elif all(isinstance(p, tuple) for p in parts) and not any(isinstance(p, FP8BTensor) for p in parts):
             w = (torch.cat([p[0] for p in parts], dim=0), torch.cat([p[1] for p in parts], dim=0))
         else:
-            w = torch.cat([dequantize_fp8(*p) if isinstance(p, tuple) else p for p in parts], dim=0)
+            w = torch.cat([deq(p) for p in parts], dim=0)
         if isinstance(w, tuple) and not fp8:
-            w = dequantize_fp8(*w)
+            w = deq(w)
         got = tuple(w[0].shape if isinstance(w, tuple) else w.shape)
         assert got == tuple(shape), f"{name}: {got} != {shape}"
         if isinstance(w, tuple):
-            yield name, ((w[0].to(out_device), w[1].to(out_device)) if out_device is not None else w)
+            if out_device is not None:
+                moved = (w[0].to(out_device), w[1].to(out_device))
+                w = FP8BTensor(*moved) if isinstance(w, FP8BTensor) else moved
+            yield name, w
             continue
         w = shard_param(cfg, name, w, rank, tp)
         yield name, (w.to(out_device) if out_device is not None else w)
