@@ -88,6 +88,13 @@ class Config:
     # fp32 scale per layer, K or V, and kv head (include/ssd_hip_kv8.h; all 1.0 unless HipDecoder.set_kv_scales is called).  Orthogonal
     # to `quantization`.  The draft's cache, q and every activation stay bf16.
     kv_cache_dtype: str | None = None
+    # LoRA adapters on the TARGET's decoder linears (not in the reference; ssd_amd/lora.py, include/ssd_hip_lora.h): up to max_loras
+    # adapters of rank <= max_lora_rank live in fixed slots beside the weights (LLM.add_lora / remove_lora / list_loras), and a request
+    # names one with SamplingParams(lora=name).  Off: nothing is allocated, staged, launched or named differently.  Drafts are never
+    # adapted (outputs stay exact, acceptance drops).
+    enable_lora: bool = False
+    max_loras: int = 4
+    max_lora_rank: int = 64
 
     @property
     def max_blocks(self) -> int:
@@ -116,6 +123,15 @@ class Config:
         if self.kv_cache_dtype is not None and self.use_eagle:
             raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r} is not supported with use_eagle=True (EAGLE-3 taps need the bf16 "
                              "target path)")
+        if self.enable_lora:
+            if isinstance(self.max_loras, bool) or not isinstance(self.max_loras, int) or not 1 <= self.max_loras <= 8:
+                raise ValueError(f"max_loras must be an integer in 1..8, got {self.max_loras!r}")
+            if self.max_lora_rank not in (16, 32, 64):
+                raise ValueError(f"max_lora_rank must be 16, 32 or 64, got {self.max_lora_rank!r}")
+            if self.num_gpus > 1:
+                raise ValueError("enable_lora=True runs on one GPU only: tensor-parallel adapters are not supported")
+            if self.use_eagle:
+                raise ValueError("enable_lora=True is not supported with use_eagle=True (EAGLE-3 taps need the fused bf16 target path)")
         assert self.num_draft_gpus >= 1 and (self.num_draft_gpus == 1 or (self.speculate and self.draft_async)), \
             "num_draft_gpus > 1 needs draft_async"
         if self.hf_config is None:

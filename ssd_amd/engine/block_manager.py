@@ -55,6 +55,12 @@ class BlockManager:
         h.update(np.array(token_ids).tobytes())
         return h.intdigest()
 
+    def _root(self, seq) -> int:
+        """What the hash chain of a sequence starts from: -1, or in the TARGET's cache the 64-bit identity of the adapter registration
+        the request runs on (Sequence.lora_id, unique per add_lora call), so a base request and an adapted one -- or two adapters, or
+        a name registered again -- never share KV blocks, and two requests on one adapter do.  The draft is never adapted."""
+        return -1 if self.is_draft else getattr(seq, "lora_id", -1)
+
     # ---- helpers ----
     def _table(self, seq) -> list[int]:
         return seq.draft_block_table if self.is_draft else seq.block_table
@@ -87,7 +93,7 @@ class BlockManager:
         assert not table
         # a sequence whose prompt is still to be scored (SamplingParams.prompt_logprobs) needs every row of it computed: the target
         # gives it fresh blocks, and still hashes and registers its full blocks below, so later requests hit them
-        h, missed = -1, not self.prefix_cache or (not self.is_draft and getattr(seq, "needs_prompt_logprobs", False))
+        h, missed = self._root(seq), not self.prefix_cache or (not self.is_draft and getattr(seq, "needs_prompt_logprobs", False))
         for i in range(seq.num_blocks):
             toks = seq.block(i)
             h = self.compute_hash(toks, h) if len(toks) == self.block_size else -1
@@ -156,12 +162,12 @@ class BlockManager:
         second-to-last table entry, the hash lands on the last one)."""
         toks = seq.block(block_index)
         if block_index == len(table) - 1:
-            prefix = self.blocks[table[-2]].hash if len(table) > 1 else -1
+            prefix = self.blocks[table[-2]].hash if len(table) > 1 else self._root(seq)
             last = self.blocks[table[-1]]
         else:
             # a block whose hashing was postponed (deferred draft KV deposit, scheduler._commit_suffix) is no longer the
             # last one: chain from ITS predecessor and label IT
-            prefix = self.blocks[table[block_index - 1]].hash if block_index > 0 else -1
+            prefix = self.blocks[table[block_index - 1]].hash if block_index > 0 else self._root(seq)
             last = self.blocks[table[block_index]]
         h = self.compute_hash(toks, prefix)
         last.update(h, toks)

@@ -98,6 +98,10 @@ class LLMEngine:
         factory = runner_factory or hip_runner_factory
 
         self.draft_runner = None
+        self.loras = None           # enable_lora: the registry of the adapter slots (ssd_amd/lora.py), else None
+        if config.enable_lora:
+            from ssd_amd.lora import LoraRegistry
+            self.loras = LoraRegistry(config.max_loras)
         self._capped_ids: set[int] = set()
         self._logprobs_out: dict[int, list] = {}        # seq id -> the records of a finished request that asked (step() fills it)
         self._prompt_logprobs_out: dict[int, list] = {}     # seq id -> the prompt records of a finished request that asked (likewise)
@@ -224,7 +228,48 @@ class LLMEngine:
         guided = sp.active_guides if sp is not None else []
         self._refuse(both, "supports_guided_decoding", guided, "this runner has no guided decoding")
         guide = self._check_guide(sp) if guided else None
-        self.scheduler.add(Sequence(prompt, sampling_params, guide=guide))
+        lora = None
+        if sp is not None and sp.lora is not None:
+            # the adapter runs on the target alone (drafts are never adapted: the verify keeps the output exact)
+            runner = getattr(self, "model_runner", None)
+            self._refuse([r for r in both if r is runner], "supports_lora", ["lora"], "this runner has no adapter kernels")
+            if self.loras is None:
+                raise ValueError(f"lora={sp.lora!r} needs an engine built with enable_lora=True")
+            lora = self.loras.resolve(sp.lora)      # ValueError naming lora for an unknown name
+        self.scheduler.add(Sequence(prompt, sampling_params, guide=guide, lora=lora))
+
+    # ---- LoRA adapters (ssd_amd/lora.py): fixed slots, no paging, no LRU -----------------------------
+    def _lora_runner(self):
+        if self.loras is None:
+            raise ValueError("LoRA adapters need an engine built with enable_lora=True")
+        runner = getattr(self, "model_runner", None)
+        if runner is None or not getattr(runner, "supports_lora", False):
+            raise ValueError(f"lora adapters are not supported by {type(runner).__name__}: this runner has no adapter kernels")
+        return runner
+
+    def add_lora(self, name: str, source, *, alpha: float | None = None) -> None:
+        """Register an adapter under `name`: `source` is a PEFT adapter directory or the in-memory dict (ssd_amd/lora.py); `alpha`
+        overrides its lora_alpha.  It is copied into a free slot; with none free the call is refused, naming the adapters that hold
+        them."""
+        from ssd_amd.lora import load_adapter
+        runner = self._lora_runner()
+        slot = self.loras.free_slot(name)
+        adapter = load_adapter(source, self.config.hf_config, self.config.max_lora_rank, alpha)
+        runner.model.set_lora(slot, adapter)
+        self.loras.add(name, slot)
+
+    def remove_lora(self, name: str) -> None:
+        """Free the adapter's slot.  Refused while a running or waiting request names it."""
+        self._lora_runner()
+        self.loras.resolve(name)
+        users = [s.seq_id for s in list(self.scheduler.running) + list(self.scheduler.waiting) if getattr(s, "lora", None) == name]
+        if users:
+            raise ValueError(f"lora {name!r} is in use by {len(users)} running or waiting request(s): it cannot be removed now")
+        self.model_runner.model.clear_lora(self.loras.remove(name))
+
+    def list_loras(self) -> list[str]:
+        """Names of the registered adapters, in slot order."""
+        return [] if self.loras is None else self.loras.names()
 
     @staticmethod
     def _refuse(runners, attr: str, fields, phrase: str) -> None:

@@ -72,6 +72,7 @@ class ModelRunner:
     supports_seed = True            # SamplingParams(seed=S): the request's own random stream (csrc/seeded.hip); likewise
     supports_logit_constraints = True   # min_tokens / allowed_token_ids / bad_words_ids (csrc/constrain.hip); likewise
     supports_guided_decoding = True     # guided_automaton / guided_choice_ids (csrc/guide.hip); likewise
+    supports_lora = True                # SamplingParams(lora=name): per-row adapter deltas on the target (csrc/lora.hip); likewise
     PENALTY_MAX_BIAS = Penalties.MAX_BIAS       # logit_bias entries one request may carry
 
     PROMPT_LOGPROB_ROWS = 512       # default of prompt_logprob_rows: the fastest of 128 / 256 / 512 per prompt row ("Prompt log-probabilities")
@@ -115,6 +116,10 @@ class ModelRunner:
         kv_cache_dtype = None if is_draft else getattr(config, "kv_cache_dtype", None)
         if kv_cache_dtype:
             qkw["kv_cache_dtype"] = kv_cache_dtype
+        # LoRA adapters live on the target alone (drafts are never adapted); the tables are part of the decoder, so they are
+        # allocated before the KV cache below is sized from what is left
+        if not is_draft and getattr(config, "enable_lora", False):
+            qkw.update(max_loras=config.max_loras, max_lora_rank=config.max_lora_rank)
         self.model = model_cls(model_cfg, max_tokens=max_tokens, max_seqs=self.max_bs, max_blocks=self.max_blocks,
                                block_size=self.block_size, max_model_len=config.max_model_len, device=device,
                                tp_rank=tp_rank, tp_size=tp_size, tp_group=tp_group,
@@ -327,6 +332,21 @@ class ModelRunner:
             rows.append(t + [-1] * (self.max_blocks - len(t)))
         self._upload(self.d_bt, rows, torch.int32)
 
+    def _lora_mark(self, seqs) -> str:
+        """"_a" when the batch has a row on an adapter: what its graph keys carry behind the sampling suffix.  The adapted forward is
+        another launch sequence; WHICH adapters it runs is data (the row_slot array), so another adapter replays the same graphs."""
+        return "_a" if getattr(self.model, "max_loras", 0) and any(getattr(s, "lora_slot", -1) >= 0 for s in seqs) else ""
+
+    def _stage_lora(self, seqs, rows) -> None:
+        """With the other inputs of a step: the slot of every token row (rows[i] rows of sequence i: the new tokens of a prefill, one
+        decode row, the K + 1 verify rows), and the route the forward about to run or be captured takes."""
+        if not getattr(self.model, "max_loras", 0):
+            return
+        on = bool(self._lora_mark(seqs))
+        self.model.lora_active = on
+        if on:
+            self._upload(self.model.lora_rows, [s.lora_slot for s, n in zip(seqs, rows) for _ in range(n)], torch.int32)
+
     def _prepare_prefill(self, seqs) -> tuple[int, int]:
         """prepare_prefill_tensors_from_seqs (runner_helpers.py:123-180): new tokens of each sequence, their
         positions and slots; context length = whole sequence (keys already cached by a prefix hit included)."""
@@ -354,6 +374,7 @@ class ModelRunner:
         self._upload(self.d_cu_q, cu, torch.int32)
         self._upload(self.d_gather, gather, torch.int32)
         self._upload_block_tables(seqs)
+        self._stage_lora(seqs, [cu[i + 1] - cu[i] for i in range(len(seqs))])
         return T, max_q
 
     def _prepare_decode(self, seqs, back: int = 0) -> int:
@@ -374,6 +395,7 @@ class ModelRunner:
         self._upload(self.d_slots, slots, torch.int32)
         self._upload(self.d_ctx, ctx, torch.int32)
         self._upload_block_tables(seqs)
+        self._stage_lora(seqs, [1] * len(seqs))
         return len(seqs)
 
     def _prepare_verify(self, seqs, ids_from_seq: bool) -> int:
@@ -397,6 +419,7 @@ class ModelRunner:
         self._upload(self.d_slots, slots, torch.int32)
         self._upload(self.d_ctx, ctx, torch.int32)
         self._upload_block_tables(seqs)
+        self._stage_lora(seqs, [K + 1] * len(seqs))
         return len(seqs) * (K + 1)
 
     # ---------------------------------------------------------------------------------------------
@@ -618,7 +641,7 @@ class ModelRunner:
             # occurrence of a shape runs purely eagerly (no sync, no capture: with free-form prompt lengths almost every
             # prefill is a new shape); the second occurrence captures (its eager warm-up run is this call's result), later
             # ones replay.  A few graphs are kept, the oldest is dropped.
-            key = ("prefill", B, T, max_q)
+            key = ("prefill" + self._lora_mark(seqs), B, T, max_q)
             full = (*key, self._ctx_hint)
             # a prefill that must score prompt rows runs eagerly and is never captured: forward, the prompt pass over its rows,
             # then the usual last-row logits
@@ -635,8 +658,8 @@ class ModelRunner:
                 self._prefill_seen[full] = 1
                 body()
             else:
-                if full not in self.graphs and sum(1 for k in self.graphs if k[0] == "prefill") >= self.PREFILL_GRAPHS:
-                    for k in [k for k in self.graphs if k[0] == "prefill"][:1]:
+                if full not in self.graphs and sum(1 for k in self.graphs if k[0].startswith("prefill")) >= self.PREFILL_GRAPHS:
+                    for k in [k for k in self.graphs if k[0].startswith("prefill")][:1]:
                         del self.graphs[k]
                 self._launch(key, body)             # "captured": the eager warm-up run already produced this call's result
             self._log_margins(B, [(s.seq_id, len(s)) for s in seqs])
@@ -648,7 +671,7 @@ class ModelRunner:
                 self.last_prompt_logprobs = self.prompt_logprobs.records(seqs, starts, scored=max(self._prompt_ntop) >= 0)
             return (toks, self.model.full_logits(B)) if draft_return_logits else toks
         if not last_only:
-            self._run_graph(("verify_logits", B), lambda: self._prepare_verify(seqs, ids_from_seq=True), lambda: self._body_verify(B, False))
+            self._run_graph(("verify_logits" + self._lora_mark(seqs), B), lambda: self._prepare_verify(seqs, ids_from_seq=True), lambda: self._body_verify(B, False))
             return self.model.full_logits(B * (self.K + 1))
         how, values = self._seq_sampling(seqs)      # greedy, autoregressive sampling (AutoRegressiveStep at temperature > 0), penalised
 
@@ -656,7 +679,7 @@ class ModelRunner:
             self._prepare_decode(seqs)
             self._stage_sampling(how, **values)
 
-        self._run_graph(("decode" + how.suffix, B), stage, lambda: self._body_decode(B, False, how=how))
+        self._run_graph(("decode" + how.suffix + self._lora_mark(seqs), B), stage, lambda: self._body_decode(B, False, how=how))
         self._log_margins(B, [(s.seq_id, len(s)) for s in seqs])
         toks = self._read_tokens(B, lp=how.lp)
         if how.lp:
@@ -887,7 +910,7 @@ class ModelRunner:
             # (penalties: token_ids ends in the K speculated positions, row j reads those from the inputs)
             self._stage_sampling(how, **values, back=K, temps_q=temps_q, ratio_rows=ratio_rows)
 
-        self._run_graph(("verify" + how.suffix, B), stage, lambda: self._body_verify(B, True, logits_q=logits_q, how=how))
+        self._run_graph(("verify" + how.suffix + self._lora_mark(seqs), B), stage, lambda: self._body_verify(B, True, logits_q=logits_q, how=how))
         self._log_margins(B * (K + 1), [(s.seq_id, s.num_tokens - (K + 1) + j + 1) for s in seqs for j in range(K + 1)])
         self.h_packed[:B].copy_(self.d_packed[:B], non_blocking=True)
         if how.lp:

@@ -23,9 +23,14 @@ class Sequence:
     counter = count()       # process-global, monotonically increasing seq ids (reference sequence.py:15,28)
     block_size = 256        # set by the engine from Config.kvcache_block_size
 
-    def __init__(self, token_ids: list[int], sampling_params: SamplingParams | None = None, guide=None):
-        """guide: the TokenAutomaton LLMEngine.add_request compiled from guided_choice_ids (it needs the engine's EOS)."""
+    def __init__(self, token_ids: list[int], sampling_params: SamplingParams | None = None, guide=None, lora=None):
+        """guide: the TokenAutomaton LLMEngine.add_request compiled from guided_choice_ids (it needs the engine's EOS).
+        lora: (slot, identity) of the adapter registration LLMEngine.add_request resolved SamplingParams.lora to."""
         sp = sampling_params or SamplingParams()
+        # LoRA adapter (ssd_amd/lora.py; None / -1 = off): the name, the slot the target's rows name, and the 64-bit identity of the
+        # registration the target's block hashes start from.  They stay with the sequence through preemption and re-prefill
+        self.lora = sp.lora if lora is not None else None
+        self.lora_slot, self.lora_id = lora if lora is not None else (-1, -1)
         self.seq_id = next(Sequence.counter)
         self.status = SequenceStatus.WAITING
         self.token_ids = list(token_ids)

@@ -27,6 +27,8 @@ from ssd_amd.hip import w4_ops as W4
 from ssd_amd.hip import w4zp_ops as W4Z
 from ssd_amd.hip import mx4_ops as MX4
 from ssd_amd.hip import kv8_ops as KV8
+from ssd_amd.hip import lora_ops as LO
+from ssd_amd import lora as LR
 from ssd_amd import quant
 from ssd_amd.model_config import ModelConfig
 
@@ -78,8 +80,17 @@ class HipDecoder:
                  max_model_len: int, device: torch.device, tp_rank: int = 0, tp_size: int = 1, tp_group=None,
                  max_logit_rows: int | None = None, max_split_tokens: int = 256, force_collectives: bool = False,
                  taps: list[int] | None = None, quantization: str | None = None, w4_zero_point: bool = False,
-                 kv_cache_dtype: str | None = None):
+                 kv_cache_dtype: str | None = None, max_loras: int = 0, max_lora_rank: int = 64):
         self.cfg, self.device = cfg, device
+        # max_loras > 0 (Config.enable_lora): slot tables of LoRA adapters for the four linears of every layer (include/ssd_hip_lora.h,
+        # ssd_amd/lora.py), allocated once at the end of __init__ -- before the KV cache is sized, so their memory is counted.  A
+        # forward whose batch has an adapted row (lora_active, set by the runner with the row_slot array) takes the ROWS route of
+        # every linear, as the quantized targets do, and adds the delta to those rows; a forward without one is launch for launch the
+        # forward of a decoder without tables.  Single rank, no taps.
+        assert max_loras == 0 or (tp_size == 1 and not force_collectives and taps is None), "LoRA targets are single-rank, without taps"
+        assert max_loras == 0 or (1 <= max_loras <= LR.MAX_LORAS and max_lora_rank in LR.RANKS), (max_loras, max_lora_rank)
+        self.max_loras, self.max_lora_rank = max_loras, max_lora_rank
+        self.lora_active = False
         # kv_cache_dtype="fp8": the paged KV cache holds e4m3 codes, one byte per element, with one fp32 scale per layer, K or V, and kv
         # head (include/ssd_hip_kv8.h; all 1.0 until set_kv_scales).  Orthogonal to `quantization`.  Every form that writes or reads KV
         # inside another kernel is off -- the QKV + RoPE epilogue of gemm_fused (and with it the fused norm prologues, whose residual
@@ -263,6 +274,62 @@ class HipDecoder:
         self.am_words = self.max_logit_rows + (self.max_logit_rows + 1) // 2
         self.am_pack_l = z(self.am_words, dtype=torch.int64)
         self.am_pack = z(tp_size, self.am_words, dtype=torch.int64)
+        if max_loras:
+            self._alloc_lora(z)
+
+    # ---- LoRA adapters -----------------------------------------------------------------------------
+    LORA_SPLIT_MAX_T = 256      # forwards of up to this many rows split the shrink's K over the default number of workgroups; longer
+                                # (prefill-sized) ones have the rows to fill the chip and keep one slab
+
+    def _alloc_lora(self, z) -> None:
+        """Everything the adapted route needs, once: the slot tables per layer and linear (their pointers are baked into hipGraphs),
+        the scale table, the row_slot array, the shrink workspace, and bf16 rows [max_tokens][2 I] for gate_up, which otherwise
+        never exists as rows (1.9 GB at the 70B shapes with 16384 rows)."""
+        cfg, S, T = self.cfg, self.max_loras, self.max_tokens
+        self.lora_geo = {lin: LR.linear_shape(lin, cfg) + (LR.slot_rank(lin, self.max_lora_rank),) for lin in LR.LINEARS}   # (N, K, R)
+        self.lora_a = {(li, lin): z(S * R * K) for li in range(cfg.num_layers) for lin, (N, K, R) in self.lora_geo.items()}
+        self.lora_b = {(li, lin): z(S * N * R) for li in range(cfg.num_layers) for lin, (N, K, R) in self.lora_geo.items()}
+        self.lora_scale = z(S, dtype=torch.float32)
+        self.lora_rows = torch.full((T,), -1, dtype=torch.int32, device=self.device)
+        Rmax = max(R for _, _, R in self.lora_geo.values())
+        self.lora_ws = z(max(LO.MAX_SPLITS * min(T, self.LORA_SPLIT_MAX_T), T) * Rmax, dtype=torch.float32)
+        self.buf_gu = z(T, 2 * self.I)
+
+    def lora_bytes(self) -> int:
+        """Device bytes the adapter support takes beside the weights (0 without it)."""
+        if not self.max_loras:
+            return 0
+        ts = list(self.lora_a.values()) + list(self.lora_b.values()) + [self.lora_scale, self.lora_rows, self.lora_ws, self.buf_gu]
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def set_lora(self, slot: int, adapter) -> None:
+        """Copy a ssd_amd.lora.LoraAdapter into slot `slot` of every table (packed per fused linear, zero-padded to the slot's rank,
+        re-tiled fragment-major) and set the slot's scale.  Adapters are data: the graphs that ran another adapter run this one."""
+        assert 0 <= slot < self.max_loras
+        for (li, lin), a_tab in self.lora_a.items():
+            N, K, R = self.lora_geo[lin]
+            A, B = LR.pack_linear(adapter, li, lin, self.cfg, R)
+            H.rows_to_frag(A.to(self.device), a_tab[slot * R * K:(slot + 1) * R * K], R, K)
+            H.rows_to_frag(B.to(self.device), self.lora_b[(li, lin)][slot * N * R:(slot + 1) * N * R], N, R)
+        self.lora_scale[slot] = adapter.scale
+        torch.cuda.synchronize(self.device)
+
+    def clear_lora(self, slot: int) -> None:
+        assert 0 <= slot < self.max_loras
+        for (li, lin), a_tab in self.lora_a.items():
+            N, K, R = self.lora_geo[lin]
+            a_tab[slot * R * K:(slot + 1) * R * K].zero_()
+            self.lora_b[(li, lin)][slot * N * R:(slot + 1) * N * R].zero_()
+        self.lora_scale[slot] = 0.0
+        torch.cuda.synchronize(self.device)
+
+    def _lora_delta(self, li: int, lin: str, xf, y, T: int, ldy: int, act_frag=None) -> None:
+        """shrink + expand of layer li's linear `lin` on the rows y its GEMM has just stored from the activations xf."""
+        N, K, R = self.lora_geo[lin]
+        S = 0 if T <= self.LORA_SPLIT_MAX_T else 1
+        LO.lora_shrink(xf, self.lora_a[(li, lin)], self.lora_rows, self.lora_ws, T, K, R, self.max_loras, S)
+        LO.lora_expand(self.lora_ws, self.lora_b[(li, lin)], self.lora_scale, self.lora_rows, y, ldy, T, N, K, R, self.max_loras, S,
+                       LO.EPI_ADD if act_frag is None else LO.EPI_SILU, act_frag)
 
     # ---------------------------------------------------------------------------------------------
     def load_weights(self, weight_iter) -> None:
@@ -768,6 +835,9 @@ class HipDecoder:
         cfg, w = self.cfg, self.w
         p = f"model.layers.{li}."
         small, norm_fuse = self.fusion_plan(T)
+        lora = self.lora_active
+        if lora:            # the rows route: norm -> rows GEMM -> delta -> RoPE / KV store
+            small = norm_fuse = False
         kc, vc = self.kv_cache[li, 0], self.kv_cache[li, 1]
         rope = dict(positions=positions, cos_sin=self.cos_sin, slots=slot_mapping, q_out=self.buf_q, k_cache=kc, v_cache=vc,
                     nh=self.nh, nkv=self.nkv, hd=self.hd, block_size=self.block_size)
@@ -783,12 +853,12 @@ class HipDecoder:
             return
         if not gemm_only:
             self._add_norm(src, T, w[p + "input_layernorm.weight"], res_in=res_in, res_out=res, out_frag=xf)
-        if small or (16 < T <= 32 and not cfg.qk_norm and not self.quantized and not self.kv8):      # T in 17..32 (tree-decode step): the two-token-tile variant
+        if small or (16 < T <= 32 and not cfg.qk_norm and not self.quantized and not self.kv8 and not lora):      # T in 17..32 (tree-decode step): the two-token-tile variant
             H.gemm_fused(wq, T, self.qkv_n, self.h, H.FEPI_QKV_ROPE, x_frag=xf, bias=bias, **rope)
             return
         head_norm = dict(q_norm_w=w.get(p + "self_attn.q_norm.weight"), k_norm_w=w.get(p + "self_attn.k_norm.weight"), eps=cfg.rms_norm_eps,
                          qkv_perm=1)
-        if not gemm_only and not self.kv8 and bias is None and self._pf_partials_ok(T, self.qkv_n, self.h):
+        if not gemm_only and not self.kv8 and not lora and bias is None and self._pf_partials_ok(T, self.qkv_n, self.h):
             # single-chunk prefill of a big QKV matrix: its split-K slabs stay in the workspace and the RoPE / KV-store kernel
             # sums them (bit-identical to the GEMM's epilogue launch + rope_store_kv; one launch less per layer)
             qkv = self._gemm_pf_partials(xf, self.h, wq, self.qkv_n, T, min_splits=2)
@@ -800,6 +870,8 @@ class HipDecoder:
                    zero=w.get(p + "self_attn.qkv_proj.weight_zero"), bscale=w.get(p + "self_attn.qkv_proj.weight_bscale"))
         if gemm_only:
             return
+        if lora:
+            self._lora_delta(li, "qkv", xf, self.buf_qkv, T, self.qkv_n)
         if self.kv8:
             KV8.rope_store_kv_fp8(self.buf_qkv, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
                                   self.hd, self.block_size, k_inv_scale=self.kv_inv_scale[li, 0], v_inv_scale=self.kv_inv_scale[li, 1],
@@ -815,6 +887,11 @@ class HipDecoder:
         name, xf, K, slabs = ((f"model.layers.{li}.self_attn.o_proj.weight", self.buf_af, self.qn, self.buf_parts_o) if which == "o" else
                               (f"model.layers.{li}.mlp.down_proj.weight", self.buf_actf, self.I, self.buf_parts_d))
         w = self.w[name]
+        if self.lora_active:        # rows into buf_h, then the delta: no slabs of any kind
+            self._gemm(xf, K, w, self.h, self.buf_h, T, self.h, scale=self.w.get(name + "_scale"), zero=self.w.get(name + "_zero"),
+                       bscale=self.w.get(name + "_bscale"))
+            self._lora_delta(li, "o" if which == "o" else "down", xf, self.buf_h, T, self.h)
+            return None
         if pf_partials and self._pf_partials_ok(T, self.h, K):
             return self._gemm_pf_partials(xf, K, w, self.h, T)
         if self.parts_plan(T) if parts is None else parts:
@@ -834,6 +911,14 @@ class HipDecoder:
         p = f"model.layers.{li}."
         if src is _PLAN:
             src = self._plan_src("o", T)
+        if self.lora_active:        # rows in the packed gate / up order -> delta -> SiLU * mul of the updated rows, fragment-major
+            if not gemm_only:
+                self._add_norm(src, T, w[p + "post_attention_layernorm.weight"], res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
+            self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_gu, T, 2 * self.I, epi=H.EPI_ROWS,
+                       scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"),
+                       bscale=w.get(p + "mlp.gate_up_proj.weight_bscale"))
+            self._lora_delta(li, "gate_up", self.buf_xf, self.buf_gu, T, 2 * self.I, act_frag=self.buf_actf)
+            return
         if self.fusion_plan(T)[1]:
             H.gemm_fused(w[p + "mlp.gate_up_proj.weight"], T, 2 * self.I, self.h, H.FEPI_SILU_FRAG,
                          res_in=self.buf_res2, res_out=self.buf_res, norm_w=w[p + "post_attention_layernorm.weight"],
@@ -861,14 +946,16 @@ class HipDecoder:
         # compute_logits, which always follows in the same Python body, reads the last hand-off: the segments leave rows (buf_h) + the
         # residual (buf_res)
         self._last = None
-        if self.chain_plan(T, meta, splits):
+        lora = self.lora_active
+        assert not lora or (self.max_loras and meta.mode == H.MODE_CAUSAL), "an adapted forward needs the slot tables and causal rows"
+        if not lora and self.chain_plan(T, meta, splits):
             self._forward_chain(positions, meta, attn_waves)
             return
-        if self.tree_plan(T, meta):
+        if not lora and self.tree_plan(T, meta):
             self._forward_tree_seg(positions, T, meta, splits, attn_waves)
             return
         # a varlen prefill never takes the slab path (its last-token gather reads rows)
-        parts = self.parts_plan(T) and meta.cu_q is None
+        parts = self.parts_plan(T) and meta.cu_q is None and not lora
         fuse_ao = parts and self.attn_o_plan(T, meta, splits)
         # tensor parallel with the one-shot collective: the all-reduce after o_proj / down_proj absorbs the residual add
         # and the RMSNorm that follow it (csrc/comm.hip), 2 launches fewer per half layer

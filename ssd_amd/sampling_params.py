@@ -34,7 +34,11 @@ it cannot go with ``ignore_eos``).  At most one of the two may be given.  The gu
 the temperature, the truncation, the draw and the argmax, raw log-probabilities read in front of it -- and independently of them; a
 position at which the composition leaves nothing allowed (``min_tokens`` holding the EOS back at the end of a choice, say) is the
 caller's error and is not guarded.  A guided request ends as every request does: on the EOS, a stop id or ``max_new_tokens``.
-Compilers from regular expressions or JSON schemas to an automaton need a tokenizer and are not offered."""
+Compilers from regular expressions or JSON schemas to an automaton need a tokenizer and are not offered.
+
+``lora=name`` runs the request on the target with the adapter registered under that name (``LLM.add_lora``; ssd_amd/lora.py,
+include/ssd_hip_lora.h).  The engine needs ``enable_lora=True``; an unknown name is refused by ``LLMEngine.add_request``.  Drafts are
+never adapted: the output is exactly the adapted target's, whatever the draft proposes."""
 import math
 from dataclasses import dataclass
 
@@ -78,6 +82,7 @@ class SamplingParams:
     bad_words_ids: list | None = None       # token sequences that must not appear (Hugging Face NoBadWordsLogitsProcessor); None = off
     guided_automaton: TokenAutomaton | None = None      # only what the automaton's current state allows may be generated; None = off
     guided_choice_ids: list | None = None   # the output is one of these token sequences, then the EOS; None = off
+    lora: str | None = None                 # name of a registered adapter the target applies to this request; None = off
 
     def __post_init__(self):
         if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or self.top_k < 0:
@@ -142,6 +147,8 @@ class SamplingParams:
                 raise ValueError("allowed_token_ids leaves nothing to generate before min_tokens: every id that is not a one-token "
                                  "entry of bad_words_ids is in stop_token_ids")
 
+        if self.lora is not None and (not isinstance(self.lora, str) or not self.lora):
+            raise ValueError(f"lora must be None (off) or the non-empty name of a registered adapter, got {self.lora!r}")
         if self.guided_automaton is not None and self.guided_choice_ids is not None:
             raise ValueError("guided_automaton and guided_choice_ids cannot both be given: a request follows one guide")
         if self.guided_automaton is not None and not isinstance(self.guided_automaton, TokenAutomaton):
