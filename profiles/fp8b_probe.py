@@ -149,13 +149,7 @@ def step(args):
     if args.block:
         from ssd_amd import quant
         from ssd_amd.model import HipDecoder
-        per_row = HipDecoder._load_fp8
-
-        def block_load(self, name, w):
-            if not isinstance(w, tuple):
-                w = quant.quantize_fp8_block(w.to(self.device))
-            per_row(self, name, w)
-        HipDecoder._load_fp8 = block_load
+        HipDecoder._quantize_on_load = lambda self, w: quant.quantize_fp8_block(w)      # bf16 linears become block-scaled on load
     print(json.dumps({"probe": "mode", "quant": "fp8", "block_scaled": bool(args.block), "reading": "single"}), flush=True)
     P.step(args)
 

@@ -102,17 +102,13 @@ class HipDecoder:
         if self.kv8 and cfg.head_dim not in (64, 128):
             raise ValueError(f"kv_cache_dtype='fp8' needs head_dim 64 or 128, got {cfg.head_dim}")
         assert not self.kv8 or (tp_size == 1 and not force_collectives and taps is None), "fp8 KV caches are single-rank, without taps"
-        # quantization="fp8": the decoder linears are e4m3 codes + per-row fp32 scales (ssd_amd/quant.py) and run on csrc/gemm_fp8.hip;
-        # every bf16-only fused form (norm prologues, the QKV+RoPE epilogue, split-K slabs, attention + o_proj, the resident chain /
-        # tree segments, prefill partials) is off, so a layer is norm -> GEMM -> RoPE / KV store -> attention -> GEMM -> norm -> GEMM
-        # -> GEMM.  Single rank only (Config refuses the rest).
-        # quantization="w4a16": int4 codes + one bf16 scale per row and 128-column group (ssd_amd/quant.py), run on csrc/gemm_w4a16.hip,
-        # with the same layer shape as fp8 (self.quantized turns the fused forms off for both).  A linear may carry one 4-bit zero
-        # point per row and group as well (quant.W4ZTensor from an AWQ / GPTQ checkpoint, or w4_zero_point=True for the on-load
-        # quantizer): it keeps a "<name>_zero" table and runs on the zero-point instantiations of the same kernel; symmetric and
-        # zero-point linears mix freely in one model.
-        # quantization="mxfp4": e2m1 codes + one e8m0 scale byte per row and 32-column block (ssd_amd/quant.py), run on
-        # csrc/gemm_mxfp4.hip, same layer shape again.
+        # quantization="fp8" | "w4a16" | "mxfp4": the decoder linears are codes + side tables in the format's device form (the formats
+        # and their host forms: ssd_amd/quant.py; load_weights) and run on that format's GEMM (_gemm).  Every bf16-only fused form
+        # (norm prologues, the QKV+RoPE epilogue, split-K slabs, attention + o_proj, the resident chain / tree segments, prefill
+        # partials) is off, so a layer is norm -> GEMM -> RoPE / KV store -> attention -> GEMM -> norm -> GEMM -> GEMM.  Which GEMM a
+        # linear runs on follows from the tables it has, so per-row and block-scaled fp8 linears, and symmetric and zero-point int4
+        # ones (w4_zero_point=True: the on-load quantizer makes the latter), mix freely in one model.  Single rank only (Config
+        # refuses the rest).
         assert quantization in (None, "fp8", "w4a16", "mxfp4"), quantization
         self.fp8 = quantization == "fp8"
         self.w4 = quantization == "w4a16"
@@ -333,43 +329,26 @@ class HipDecoder:
 
     # ---------------------------------------------------------------------------------------------
     def load_weights(self, weight_iter) -> None:
-        """Consumes (name, row-major bf16 shard) pairs; matrices are re-tiled once into the fragment-major
-        layout (gate_up with gate/up row groups interleaved for the fused SiLU epilogue).  A decoder linear may also come as
-        (name, (q float8_e4m3fn [N, K], s fp32 [N])) from a pre-quantized checkpoint.  An fp8 decoder quantizes each bf16 linear
-        as it arrives (never the whole model in both forms) and stores "<name>" = fp8 frag codes, "<name>_scale" = fp32 [N] in
-        the packed row order; a block-scaled quant.FP8BTensor(codes, rowscale) keeps its codes and stores "<name>_bscale" = fp32
-        [N / 16, ceil(K / 128)] instead (include/ssd_hip_fp8b.h), linear by linear.  Likewise a w4a16 decoder takes bf16 linears or quant.W4Tensor(packed, scale) from a pack-quantized
-        checkpoint and stores "<name>" = w4 frag codes, "<name>_scale" = bf16 w4 frag scales (include/ssd_hip_w4a16.h).  An mxfp4
-        decoder takes bf16 linears or quant.MX4Tensor(packed, scale) and stores "<name>" = mx4 frag codes, "<name>_scale" = mx4 frag
-        scale bytes (include/ssd_hip_mxfp4.h).  A w4a16 decoder also takes quant.W4ZTensor(packed, scale, zero) and then stores
-        "<name>_zero" = the zero-point table (include/ssd_hip_w4zp.h) next to the other two.  A bf16 decoder computes with the exact
-        dequantized matrix of whatever it is handed; a quantized decoder refuses tensors of another format."""
+        """Consumes (name, row-major bf16 shard) pairs; matrices are re-tiled once into the fragment-major layout (gate_up with
+        gate/up row groups interleaved for the fused SiLU epilogue).  A decoder linear may also come pre-quantized, as one of the
+        host forms of ssd_amd/quant.py (a plain (q, s) pair is a quant.FP8Tensor).  The rule: a quantized decoder packs a linear of
+        its own kind as it is, "<name>" = frag codes plus the "<name>_scale" / "_zero" / "_bscale" tables of that form (_load_fp8,
+        _load_w4, _load_mx4), quantizes a bf16 linear as it arrives (never the whole model in both forms) and refuses a linear of
+        another kind; everything else -- any host form into a bf16 decoder, embeddings, LM head, norms -- loads as bf16, a host
+        form as the exact dequantized matrix."""
+        kind = self._kind()
         for name, w in weight_iter:
-            if isinstance(w, quant.FP8BTensor) and not (self.fp8 and quant.is_quantized_linear(name)):
-                if self.quantized and quant.is_quantized_linear(name):
-                    raise ValueError(f"{name}: block-scaled fp8 tensors cannot load into {'a w4a16' if self.w4 else 'an mxfp4'} decoder")
-                w = quant.dequantize_fp8_block(w.codes.to(self.device), w.rowscale.to(self.device))
-            if isinstance(w, quant.W4ZTensor) and not self.w4:
-                if self.quantized:
-                    raise ValueError(f"{name}: zero-point int4 tensors cannot load into {'an fp8' if self.fp8 else 'an mxfp4'} decoder")
-                w = quant.dequantize_w4zp(w.packed.to(self.device), w.scale.to(self.device), w.zero.to(self.device))
-            if self.mx4 and quant.is_quantized_linear(name):
-                self._load_mx4(name, w)
+            if type(w) is tuple and len(w) == 2:
+                w = quant.FP8Tensor(*w)
+            if kind is not None and quant.is_quantized_linear(name):
+                if not quant.is_prequantized(w):
+                    w = self._quantize_on_load(w.to(self.device))
+                elif w.native != kind:
+                    raise ValueError(f"{name}: {w.phrase} tensors cannot load into a {kind} decoder")
+                self._load_quantized(name, quant.to_device(w, self.device))
                 continue
-            if isinstance(w, quant.MX4Tensor):
-                if self.quantized:
-                    raise ValueError(f"{name}: MXFP4 tensors cannot load into a {'fp8' if self.fp8 else 'w4a16'} decoder")
-                w = quant.dequantize_mxfp4(w.packed.to(self.device), w.scale.to(self.device))
-            if self.fp8 and quant.is_quantized_linear(name):
-                self._load_fp8(name, w)
-                continue
-            if self.w4 and quant.is_quantized_linear(name):
-                self._load_w4(name, w)
-                continue
-            if isinstance(w, quant.W4Tensor):   # int4 tensors into a bf16 decoder: compute with bf16(s * q)
-                w = quant.dequantize_w4a16(w.packed.to(self.device), w.scale.to(self.device))
-            elif isinstance(w, tuple):          # pre-quantized tensors into a bf16 decoder: compute with bf16(s * q)
-                w = quant.dequantize_fp8(w[0].to(self.device), w[1].to(self.device))
+            if quant.is_prequantized(w):        # a bf16 decoder (or a matrix that stays bf16) computes with bf16(s * q)
+                w = quant.to_device(w, self.device).dequantize()
             w = w.to(self.device).contiguous()
             if name.endswith("qkv_proj.weight"):
                 # rotation-paired row order: RoPE pairs share an accumulator tile (fused epilogue) -- layout.hip
@@ -393,74 +372,69 @@ class HipDecoder:
                 self.w[name] = w
         torch.cuda.synchronize(self.device)
 
-    def _row_map(self, name: str, N: int) -> torch.Tensor | None:
-        """Source row of every packed row of a quantized [N, K] linear (QKV: rotation-paired, gate_up: interleaved), None = in order."""
+    def _kind(self) -> str | None:
+        """The `quantization` value this decoder runs, read off its flags."""
+        return "fp8" if self.fp8 else "w4a16" if self.w4 else "mxfp4" if self.mx4 else None
+
+    def _quantize_on_load(self, w: torch.Tensor):
+        """The host form this decoder's own quantizer gives a bf16 linear."""
+        if self.fp8:
+            return quant.quantize_fp8(w)
+        if self.mx4:
+            return quant.quantize_mxfp4(w)
+        return quant.quantize_w4a16_zp(w) if self.w4_zero_point else quant.quantize_w4a16(w)
+
+    def _load_quantized(self, name: str, w) -> None:
+        """A host form of this decoder's kind, on the device -> its codes and side tables in the packed row order (QKV: rotation-
+        paired, gate_up: interleaved), stored under "<name>" + the suffixes the format's loader answers with."""
+        N, K = w.shape()
+        row_map = None
         if name.endswith("qkv_proj.weight"):
-            return quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
-        if name.endswith("gate_up_proj.weight"):
-            return quant.gate_up_row_map(N).to(self.device)
-        return None
+            row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
+        elif name.endswith("gate_up_proj.weight"):
+            row_map = quant.gate_up_row_map(N).to(self.device)
+        load = self._load_fp8 if self.fp8 else self._load_mx4 if self.mx4 else self._load_w4
+        for suffix, t in load(name, w, N, K, row_map).items():
+            self.w[name + suffix] = t
 
-    def _load_fp8(self, name: str, w) -> None:
-        if isinstance(w, quant.FP8BTensor):     # block-scaled: the codes as below, the scales as a group table under "<name>_bscale"
-            q, rs = w.codes.to(self.device).contiguous(), w.rowscale.to(self.device).to(torch.float32).contiguous()
-            N, K = q.shape
-            assert q.dtype == quant.FP8 and tuple(rs.shape) == (N, -(-K // quant.FP8_BLOCK)), (name, q.dtype, rs.shape)
-            row_map = self._row_map(name, N)
-            out = torch.empty(N * K, dtype=torch.uint8, device=self.device)
-            Q.fp8_rows_to_frag(q.view(torch.uint8), out, N, K, row_map=row_map)
-            self.w[name] = out
-            self.w[name + "_bscale"] = quant.fp8_block_group_scales(rs, row_map, name)
-            return
-        q, s = (w[0].to(self.device), w[1].to(self.device)) if isinstance(w, tuple) else quant.quantize_fp8(w.to(self.device))
-        q, s = q.contiguous(), s.to(torch.float32).reshape(-1).contiguous()
-        N, K = q.shape
-        assert q.dtype == quant.FP8 and s.numel() == N, (name, q.dtype, s.shape)
-        row_map = self._row_map(name, N)
-        out = torch.empty(N * K, dtype=torch.uint8, device=self.device)
-        if row_map is not None:
-            s = s[row_map.long()].contiguous()
-        Q.fp8_rows_to_frag(q.view(torch.uint8), out, N, K, row_map=row_map)
-        self.w[name] = out
-        self.w[name + "_scale"] = s
+    def _frag(self, numel: int, dtype) -> torch.Tensor:
+        return torch.empty(numel, dtype=dtype, device=self.device)
 
-    def _load_w4(self, name: str, w) -> None:
-        if not isinstance(w, (quant.W4Tensor, quant.W4ZTensor)):
-            w = quant.quantize_w4a16_zp(w.to(self.device)) if self.w4_zero_point else quant.quantize_w4a16(w.to(self.device))
-        packed, s = w.packed.to(self.device).contiguous(), w.scale.to(self.device).to(BF16).contiguous()
-        N, K = packed.shape[0], packed.shape[1] * 8
+    def _load_fp8(self, name: str, w, N: int, K: int, row_map) -> dict:
+        """FP8Tensor -> fp8 frag codes + "_scale" fp32 [N]; FP8BTensor -> the same codes + "_bscale" fp32 [N / 16, ceil(K / 128)], one
+        scale per 16-row group and column block (include/ssd_hip_fp8b.h).  A linear has one or the other."""
+        block = isinstance(w, quant.FP8BTensor)
+        s = w.rowscale.to(torch.float32).contiguous() if block else w.scale.to(torch.float32).reshape(-1).contiguous()
+        assert w.codes.dtype == quant.FP8 and tuple(s.shape) == ((N, -(-K // quant.FP8_BLOCK)) if block else (N,)), (name, w.codes.dtype, s.shape)
+        codes = self._frag(N * K, torch.uint8)
+        Q.fp8_rows_to_frag(w.codes.contiguous().view(torch.uint8), codes, N, K, row_map=row_map)
+        if block:
+            return {"": codes, "_bscale": quant.fp8_block_group_scales(s, row_map, name)}
+        return {"": codes, "_scale": s if row_map is None else s[row_map.long()].contiguous()}
+
+    def _load_w4(self, name: str, w, N: int, K: int, row_map) -> dict:
+        """W4Tensor -> w4 frag codes + "_scale" bf16 frag scales (include/ssd_hip_w4a16.h); W4ZTensor -> those + "_zero", the zero-point
+        table (include/ssd_hip_w4zp.h)."""
+        packed, s = w.packed.contiguous(), w.scale.to(BF16).contiguous()
         assert packed.dtype == torch.int32 and tuple(s.shape) == (N, K // quant.W4_GROUP), (name, packed.dtype, s.shape)
-        zero = None
+        out = {"": self._frag(N * K // 2, torch.uint8), "_scale": self._frag(N * K // quant.W4_GROUP, BF16)}
         if isinstance(w, quant.W4ZTensor):
-            zero = w.zero.to(self.device).contiguous()
+            zero = w.zero.contiguous()
             assert zero.dtype == torch.uint8 and zero.shape == s.shape and int(zero.max()) <= 15, (name, zero.dtype, zero.shape)
-        row_map = self._row_map(name, N)
-        q_frag = torch.empty(N * K // 2, dtype=torch.uint8, device=self.device)
-        s_frag = torch.empty(N * K // quant.W4_GROUP, dtype=BF16, device=self.device)
-        if zero is not None:
-            z_frag = torch.empty(N * K // quant.W4_GROUP, dtype=torch.uint8, device=self.device)
-            W4Z.w4zp_rows_to_frag(packed, s, zero, q_frag, s_frag, z_frag, N, K, row_map=row_map)
-            self.w[name + "_zero"] = z_frag
+            out["_zero"] = self._frag(N * K // quant.W4_GROUP, torch.uint8)
+            W4Z.w4zp_rows_to_frag(packed, s, zero, out[""], out["_scale"], out["_zero"], N, K, row_map=row_map)
         else:
-            W4.w4_rows_to_frag(packed, s, q_frag, s_frag, N, K, row_map=row_map)
-        self.w[name] = q_frag
-        self.w[name + "_scale"] = s_frag
+            W4.w4_rows_to_frag(packed, s, out[""], out["_scale"], N, K, row_map=row_map)
+        return out
 
-    def _load_mx4(self, name: str, w) -> None:
-        if isinstance(w, tuple) and not isinstance(w, quant.MX4Tensor):
-            raise ValueError(f"{name}: fp8 / w4a16 tensors cannot load into an mxfp4 decoder")
-        if not isinstance(w, quant.MX4Tensor):
-            w = quant.quantize_mxfp4(w.to(self.device))
-        packed, s = w.packed.to(self.device).contiguous(), w.scale.to(self.device).contiguous()
-        N, K = packed.shape[0], packed.shape[1] * 2
+    def _load_mx4(self, name: str, w, N: int, K: int, row_map) -> dict:
+        """MX4Tensor -> mx4 frag codes + "_scale" mx4 frag scale bytes (include/ssd_hip_mxfp4.h)."""
+        packed, s = w.packed.contiguous(), w.scale.contiguous()
         assert packed.dtype == torch.uint8 and tuple(s.shape) == (N, K // quant.MX4_BLOCK), (name, packed.dtype, s.shape)
         quant.check_mxfp4_scales(name, s)
-        row_map = self._row_map(name, N)
-        q_frag = torch.empty(N * K // 2, dtype=torch.uint8, device=self.device)
-        s_frag = torch.empty(N * K // quant.MX4_BLOCK, dtype=torch.uint8, device=self.device)
-        MX4.mx4_rows_to_frag(packed, s, q_frag, s_frag, N, K, row_map=row_map)
-        self.w[name] = q_frag
-        self.w[name + "_scale"] = s_frag
+        out = {"": self._frag(N * K // 2, torch.uint8), "_scale": self._frag(N * K // quant.MX4_BLOCK, torch.uint8)}
+        MX4.mx4_rows_to_frag(packed, s, out[""], out["_scale"], N, K, row_map=row_map)
+        return out
 
     def overwrite_weights(self, weight_iter) -> None:
         """New VALUES into the existing weight tensors (same names and shapes): captured hipGraphs keep pointing at the same memory, so a
@@ -474,15 +448,8 @@ class HipDecoder:
         torch.cuda.synchronize(self.device)
 
     def _qkv_row_perm(self) -> torch.Tensor:
-        """Source row of every destination row of the rotation-paired QKV order (same map as ssd_rows_to_frag_qkv)."""
-        hd, half, gph = self.hd, self.hd // 2, self.hd // 16
-        idx = []
-        for head in range(self.nh + self.nkv):
-            for j in range(gph):
-                idx.extend(head * hd + 8 * j + i for i in range(8))
-                idx.extend(head * hd + half + 8 * j + i for i in range(8))
-        idx.extend(range((self.nh + self.nkv) * hd, (self.nh + 2 * self.nkv) * hd))
-        return torch.tensor(idx, dtype=torch.int64)
+        """quant.qkv_row_map as an index tensor: the order the bf16 QKV bias is permuted with."""
+        return quant.qkv_row_map(self.nh, self.nkv, self.hd).long()
 
     def weight_bytes(self) -> int:
         """HBM bytes one forward must stream (every matrix once; the embedding table is only gathered; fp8 or int4 codes + their
@@ -582,38 +549,36 @@ class HipDecoder:
         H.gemm_pf(xf, w, None, T, N, K, N, self._ws_pf, epilogue=H.PF_EPI_PARTIALS)
         return Slabs(self._ws_pf, S, T)
 
-    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None, scale=None, zero=None, bscale=None):
-        if bscale is not None:          # fp8 codes (w) + block scales per 16-row group (a linear has these or row scales, never both)
+    def _quant_route(self, name: str):
+        """(GEMM, dequantizer, direct limit, side tables) of a quantized linear, chosen by the tables load_weights left beside its
+        codes; None for a bf16 matrix.  The ops are read off their modules at every call: a trace or a probe may have replaced them."""
+        scale, bscale = self.w.get(name + "_scale"), self.w.get(name + "_bscale")
+        if bscale is not None:          # fp8 codes + block scales per 16-row group (a linear has these or row scales, never both)
             assert scale is None and self.fp8
-            if T <= self.FP8_DIRECT_MAX_T:
-                F8B.gemm_fp8b(xf, w, bscale, y, T, N, K, ldy, epi, bias)
-                return
-            F8B.fp8b_dequant_frag(w, bscale, self._deq, N, K)
-            w = self._deq
-        elif scale is not None and self.w4 and zero is not None:   # w4a16 codes (w) + group scales + group zero points
-            if T <= self.W4_DIRECT_MAX_T:
-                W4Z.gemm_w4a16_zp(xf, w, scale, zero, y, T, N, K, ldy, epi, bias)
-                return
-            W4Z.w4zp_dequant_frag(w, scale, zero, self._deq, N, K)
-            w = self._deq
-        elif scale is not None and self.w4:   # w4a16 codes (w) + group scales
-            if T <= self.W4_DIRECT_MAX_T:
-                W4.gemm_w4a16(xf, w, scale, y, T, N, K, ldy, epi, bias)
-                return
-            W4.w4_dequant_frag(w, scale, self._deq, N, K)
-            w = self._deq
-        elif scale is not None and self.mx4:   # mxfp4 codes (w) + block scale bytes
-            if T <= self.MX4_DIRECT_MAX_T:
-                MX4.gemm_mxfp4(xf, w, scale, y, T, N, K, ldy, epi, bias)
-                return
-            MX4.mx4_dequant_frag(w, scale, self._deq, N, K)
-            w = self._deq
-        elif scale is not None:         # fp8 codes (w) + row scales
-            if T <= self.FP8_DIRECT_MAX_T:
-                Q.gemm_fp8(xf, w, scale, y, T, N, K, ldy, epi, bias)
-                return
-            Q.fp8_dequant_frag(w, scale, self._deq, N, K)
-            w = self._deq
+            return F8B.gemm_fp8b, F8B.fp8b_dequant_frag, self.FP8_DIRECT_MAX_T, (bscale,)
+        if scale is None:
+            return None
+        if self.w4:                     # w4a16 codes + group scales, and group zero points where the linear has them
+            zero = self.w.get(name + "_zero")
+            if zero is not None:
+                return W4Z.gemm_w4a16_zp, W4Z.w4zp_dequant_frag, self.W4_DIRECT_MAX_T, (scale, zero)
+            return W4.gemm_w4a16, W4.w4_dequant_frag, self.W4_DIRECT_MAX_T, (scale,)
+        if self.mx4:                    # mxfp4 codes + block scale bytes
+            return MX4.gemm_mxfp4, MX4.mx4_dequant_frag, self.MX4_DIRECT_MAX_T, (scale,)
+        return Q.gemm_fp8, Q.fp8_dequant_frag, self.FP8_DIRECT_MAX_T, (scale,)      # fp8 codes + row scales
+
+    def _gemm(self, xf, K, w, N, y, T, ldy, epi=H.EPI_ROWS, bias=None):
+        """y = xf @ w^T.  w is a fragment-major bf16 matrix, or the name of a decoder linear in self.w: a quantized one runs on its
+        format's GEMM up to that format's direct limit of rows and is dequantized into self._deq for the bf16 routes beyond it."""
+        if isinstance(w, str):
+            route, w = self._quant_route(w), self.w[w]
+            if route is not None:
+                gemm, dequant, direct_max, side = route
+                if T <= direct_max:
+                    gemm(xf, w, *side, y, T, N, K, ldy, epi, bias)
+                    return
+                dequant(w, *side, self._deq, N, K)
+                w = self._deq
         if T > 128 and self._lm_eligible(T) and N % 128 == 0 and K % 128 == 0:
             assert self._ws_pf is not None and self._ws_pf.numel() * 4 >= H.gemm_pf_workspace_bytes(T, N, K), (T, N, K)
             H.gemm_pf(xf, w, y, T, N, K, ldy, self._ws_pf, epilogue=epi, bias=bias)
@@ -866,8 +831,7 @@ class HipDecoder:
                 H.rope_store_kv_parts(qkv.buf, qkv.n, positions, self.cos_sin, slot_mapping, self.buf_q, kc, vc, T, self.nh, self.nkv,
                                       self.hd, self.block_size, **head_norm)
                 return
-        self._gemm(xf, self.h, wq, self.qkv_n, self.buf_qkv, T, self.qkv_n, bias=bias, scale=w.get(p + "self_attn.qkv_proj.weight_scale"),
-                   zero=w.get(p + "self_attn.qkv_proj.weight_zero"), bscale=w.get(p + "self_attn.qkv_proj.weight_bscale"))
+        self._gemm(xf, self.h, p + "self_attn.qkv_proj.weight", self.qkv_n, self.buf_qkv, T, self.qkv_n, bias=bias)
         if gemm_only:
             return
         if lora:
@@ -888,8 +852,7 @@ class HipDecoder:
                               (f"model.layers.{li}.mlp.down_proj.weight", self.buf_actf, self.I, self.buf_parts_d))
         w = self.w[name]
         if self.lora_active:        # rows into buf_h, then the delta: no slabs of any kind
-            self._gemm(xf, K, w, self.h, self.buf_h, T, self.h, scale=self.w.get(name + "_scale"), zero=self.w.get(name + "_zero"),
-                       bscale=self.w.get(name + "_bscale"))
+            self._gemm(xf, K, name, self.h, self.buf_h, T, self.h)
             self._lora_delta(li, "o" if which == "o" else "down", xf, self.buf_h, T, self.h)
             return None
         if pf_partials and self._pf_partials_ok(T, self.h, K):
@@ -898,8 +861,7 @@ class HipDecoder:
             S, wv = self._parts(which, T)
             H.gemm_parts(xf, w, T, self.h, K, parts=slabs, splits=S, waves=wv)
             return Slabs(slabs, S, T)
-        self._gemm(xf, K, w, self.h, self.buf_h, T, self.h, scale=self.w.get(name + "_scale"), zero=self.w.get(name + "_zero"),
-                   bscale=self.w.get(name + "_bscale"))
+        self._gemm(xf, K, name, self.h, self.buf_h, T, self.h)
         return None
 
     def launch_o(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> Slabs | None:
@@ -914,9 +876,7 @@ class HipDecoder:
         if self.lora_active:        # rows in the packed gate / up order -> delta -> SiLU * mul of the updated rows, fragment-major
             if not gemm_only:
                 self._add_norm(src, T, w[p + "post_attention_layernorm.weight"], res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
-            self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_gu, T, 2 * self.I, epi=H.EPI_ROWS,
-                       scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"),
-                       bscale=w.get(p + "mlp.gate_up_proj.weight_bscale"))
+            self._gemm(self.buf_xf, self.h, p + "mlp.gate_up_proj.weight", 2 * self.I, self.buf_gu, T, 2 * self.I, epi=H.EPI_ROWS)
             self._lora_delta(li, "gate_up", self.buf_xf, self.buf_gu, T, 2 * self.I, act_frag=self.buf_actf)
             return
         if self.fusion_plan(T)[1]:
@@ -926,9 +886,7 @@ class HipDecoder:
             return
         if not gemm_only:
             self._add_norm(src, T, w[p + "post_attention_layernorm.weight"], res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)
-        self._gemm(self.buf_xf, self.h, w[p + "mlp.gate_up_proj.weight"], 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG,
-                   scale=w.get(p + "mlp.gate_up_proj.weight_scale"), zero=w.get(p + "mlp.gate_up_proj.weight_zero"),
-                   bscale=w.get(p + "mlp.gate_up_proj.weight_bscale"))
+        self._gemm(self.buf_xf, self.h, p + "mlp.gate_up_proj.weight", 2 * self.I, self.buf_actf, T, 0, epi=H.EPI_SILU_FRAG)
 
     def launch_down(self, li: int, T: int, parts: bool | None = None, pf_partials: bool = False) -> Slabs | None:
         return self._launch_to_h("d", li, T, parts, pf_partials)

@@ -25,15 +25,33 @@ def is_quantized_linear(name: str) -> bool:
     return name.startswith("model.layers.") and name.endswith(LINEAR_SUFFIXES)
 
 
-def quantize_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
-    """[N, K] bf16 -> (q [N, K] float8_e4m3fn, s [N] fp32), on w's device."""
+# Host forms.  A pre-quantized decoder linear travels from a checkpoint (or a host quantizer) to the decoder as one of five
+# NamedTuples: FP8Tensor, FP8BTensor, W4Tensor, W4ZTensor, MX4Tensor.  Each answers, here and nowhere else: `native`, the
+# `quantization` value of the target that runs it as it is; `phrase`, what refusals call it; shape(), the logical (N, K); and
+# dequantize(), the bf16 matrix such a target computes with (what a bf16 target loads instead).  Every field of every type has one
+# row per output row, so packing q | k | v or gate | up (cat_rows) and moving (to_device) are generic.
+class FP8Tensor(NamedTuple):
+    """An FP8 decoder linear with one scale per row on the host: codes float8_e4m3fn [N, K], scale fp32 [N]."""
+    codes: torch.Tensor
+    scale: torch.Tensor
+    native, phrase = "fp8", "per-row fp8"
+
+    def shape(self) -> tuple[int, int]:
+        return tuple(self.codes.shape)
+
+    def dequantize(self) -> torch.Tensor:
+        return dequantize_fp8(*self)
+
+
+def quantize_fp8(w: torch.Tensor) -> FP8Tensor:
+    """[N, K] bf16 -> FP8Tensor(q [N, K] float8_e4m3fn, s [N] fp32), on w's device."""
     wf = w.float()
     amax = wf.abs().amax(dim=1)
     amax = torch.where(amax == 0, torch.full_like(amax, FP8_MAX), amax)
     inv = FP8_MAX / amax
     s = amax / FP8_MAX
     q = (wf * inv[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)
-    return q, s
+    return FP8Tensor(q, s)
 
 
 def dequantize_fp8(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
@@ -83,6 +101,13 @@ class FP8BTensor(NamedTuple):
     the scales of the block row its source tensor put row n in)."""
     codes: torch.Tensor
     rowscale: torch.Tensor
+    native, phrase = "fp8", "block-scaled fp8"
+
+    def shape(self) -> tuple[int, int]:
+        return tuple(self.codes.shape)
+
+    def dequantize(self) -> torch.Tensor:
+        return dequantize_fp8_block(*self)
 
 
 def expand_fp8_block_scales(s: torch.Tensor, N: int) -> torch.Tensor:
@@ -151,6 +176,13 @@ class W4Tensor(NamedTuple):
     """A W4A16 decoder linear in the pack-quantized host form: packed int32 [N, K / 8], scale bf16 [N, K / 128]."""
     packed: torch.Tensor
     scale: torch.Tensor
+    native, phrase = "w4a16", "int4 (w4a16)"
+
+    def shape(self) -> tuple[int, int]:
+        return self.packed.shape[0], self.packed.shape[1] * 8
+
+    def dequantize(self) -> torch.Tensor:
+        return dequantize_w4a16(*self)
 
 
 def pack_w4(q: torch.Tensor) -> torch.Tensor:
@@ -213,6 +245,13 @@ class W4ZTensor(NamedTuple):
     packed: torch.Tensor
     scale: torch.Tensor
     zero: torch.Tensor
+    native, phrase = "w4a16", "zero-point int4"
+
+    def shape(self) -> tuple[int, int]:
+        return self.packed.shape[0], self.packed.shape[1] * 8
+
+    def dequantize(self) -> torch.Tensor:
+        return dequantize_w4zp(*self)
 
 
 def pack_w4u(u: torch.Tensor) -> torch.Tensor:
@@ -274,6 +313,13 @@ class MX4Tensor(NamedTuple):
     """An MXFP4 decoder linear in the host form: packed uint8 [N, K / 2], scale uint8 [N, K / 32]."""
     packed: torch.Tensor
     scale: torch.Tensor
+    native, phrase = "mxfp4", "MXFP4"
+
+    def shape(self) -> tuple[int, int]:
+        return self.packed.shape[0], self.packed.shape[1] * 2
+
+    def dequantize(self) -> torch.Tensor:
+        return dequantize_mxfp4(*self)
 
 
 def check_mxfp4_scales(name: str, scale: torch.Tensor) -> None:
@@ -330,6 +376,25 @@ def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     v = lut[unpack_mxfp4(packed).long()]
     s = (scale.to(torch.int32) << 23).view(torch.float32).repeat_interleave(MX4_BLOCK, dim=1)
     return (v * s).to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# What the loaders and the decoder ask of a host form without knowing which of the five it is.
+# ---------------------------------------------------------------------------------------------------------------------
+def is_prequantized(w) -> bool:
+    """Whether w is a pre-quantized decoder linear in one of the host forms (anything else is a plain tensor)."""
+    return isinstance(w, (FP8Tensor, FP8BTensor, W4Tensor, W4ZTensor, MX4Tensor))
+
+
+def cat_rows(parts: list):
+    """q | k | v or gate | up of ONE host form packed into the form of the whole matrix: every field is concatenated along the rows."""
+    assert len({type(p) for p in parts}) == 1 and is_prequantized(parts[0]), [type(p).__name__ for p in parts]
+    return type(parts[0])(*(torch.cat(field, dim=0) for field in zip(*parts)))
+
+
+def to_device(w, device):
+    """A host form with every field on `device` (None: where it is)."""
+    return w if device is None else type(w)(*(t.to(device) for t in w))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

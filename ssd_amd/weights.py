@@ -554,16 +554,10 @@ def _unpack_nibbles(words: torch.Tensor, order=None) -> torch.Tensor:
     return nib.reshape(words.shape[0], -1).to(torch.uint8)
 
 
-def _load_awq_gptq(cfg: ModelConfig, model_dir: str, scheme: dict, rank: int, tp: int, out_device: str | None,
-                   w4a16: bool) -> Iterator[tuple[str, torch.Tensor]]:
-    """The AutoAWQ / GPTQ side of load_safetensors.  A quantized linear is unpacked, transposed to [N, K] and repacked on out_device,
-    one tensor at a time; q / k / v and gate / up are concatenated into the packed names.  A w4a16 target gets
-    quant.W4ZTensor(packed, scale, zero) (fp16 scales rounded to bf16 once), or the plain symmetric W4Tensor when every zero point
-    of the linear is 8; any other target gets bf16(s * (u - z)), sharded as usual.  A linear stored only as an unquantized .weight
-    (AWQ modules_to_not_convert, the LM head), norms and embeddings load as bf16."""
+def _safetensors_index(model_dir: str, device: str | None = None):
+    """(index, raw): the file that holds every tensor name under model_dir, and raw(name) = that tensor as stored (on `device`, if
+    one is given)."""
     from safetensors import safe_open
-    from ssd_amd.quant import W4ZTensor, W4_GROUP, dequantize_w4zp, pack_w4u, w4z_as_symmetric
-    awq = scheme["method"] == AWQ_METHOD
     index: dict[str, str] = {}
     for f in sorted(glob.glob(os.path.join(model_dir, "*.safetensors"))):
         with safe_open(f, "pt", "cpu") as sf:
@@ -573,7 +567,40 @@ def _load_awq_gptq(cfg: ModelConfig, model_dir: str, scheme: dict, rank: int, tp
     def raw(name: str) -> torch.Tensor:
         with safe_open(index[name], "pt", "cpu") as sf:
             t = sf.get_tensor(name)
-        return t.to(out_device) if out_device is not None else t
+        return t.to(device) if device is not None else t
+
+    return index, raw
+
+
+def _assemble(cfg: ModelConfig, name: str, shape, parts: list, target: str | None, rank: int, tp: int, out_device: str | None):
+    """One parameter from its parts (q | k | v, gate | up, or the tensor alone), each a bf16 tensor or a host form of ssd_amd/quant.py.
+    Parts of one quantized form that the target (its `quantization` value; None: bf16) runs natively stay in that form, packed
+    row-wise; for any other target their packed form is dequantized; mixed parts are dequantized one by one and packed as bf16.
+    bf16 results are sharded as usual."""
+    from ssd_amd import quant
+    if quant.is_prequantized(parts[0]) and len({type(p) for p in parts}) == 1:
+        w = quant.cat_rows(parts)
+        if w.native == target:
+            assert w.shape() == tuple(shape), f"{name}: {w.shape()} != {shape}"
+            return quant.to_device(w, out_device)
+        w = w.dequantize()
+    else:
+        w = torch.cat([p.dequantize() if quant.is_prequantized(p) else p for p in parts], dim=0)
+    assert tuple(w.shape) == tuple(shape), f"{name}: {tuple(w.shape)} != {shape}"
+    w = shard_param(cfg, name, w, rank, tp)
+    return w.to(out_device) if out_device is not None else w
+
+
+def _load_awq_gptq(cfg: ModelConfig, model_dir: str, scheme: dict, rank: int, tp: int, out_device: str | None,
+                   w4a16: bool) -> Iterator[tuple[str, torch.Tensor]]:
+    """The AutoAWQ / GPTQ side of load_safetensors.  A quantized linear is unpacked, transposed to [N, K] and repacked on out_device,
+    one tensor at a time; q / k / v and gate / up are concatenated into the packed names.  A w4a16 target gets
+    quant.W4ZTensor(packed, scale, zero) (fp16 scales rounded to bf16 once), or the plain symmetric W4Tensor when every zero point
+    of the linear is 8; any other target gets bf16(s * (u - z)), sharded as usual.  A linear stored only as an unquantized .weight
+    (AWQ modules_to_not_convert, the LM head), norms and embeddings load as bf16."""
+    from ssd_amd.quant import W4ZTensor, W4_GROUP, pack_w4u, w4z_as_symmetric
+    awq = scheme["method"] == AWQ_METHOD
+    index, raw = _safetensors_index(model_dir, out_device)
 
     def get_q(base: str) -> W4ZTensor:
         qw, qz, sc = raw(base + INT4_QWEIGHT_SUFFIX), raw(base + INT4_QZEROS_SUFFIX), raw(base + INT4_SCALES_SUFFIX)
@@ -613,76 +640,48 @@ def _load_awq_gptq(cfg: ModelConfig, model_dir: str, scheme: dict, rank: int, tp
         srcs = _packed_sources(name)
         whole = name in index or name[:-len(".weight")] + INT4_QWEIGHT_SUFFIX in index
         parts = [get(s) for s in srcs] if srcs is not None and not whole else [get(name)]
-        if all(isinstance(p, W4ZTensor) for p in parts):
-            w = W4ZTensor(*(torch.cat([p[i] for p in parts], dim=0) for i in range(3)))
-            assert (w.packed.shape[0], w.packed.shape[1] * 8) == tuple(shape), f"{name}: {tuple(w.packed.shape)} vs {shape}"
-            if w4a16:
-                yield name, w4z_as_symmetric(w)
-                continue
-            w = dequantize_w4zp(*w)
-        else:
-            if w4a16 and any(isinstance(p, W4ZTensor) for p in parts):
-                import warnings
-                warnings.warn(f"{name}: only some of {srcs} are quantized in the checkpoint; the packed matrix is dequantized and the "
-                              "w4a16 target quantizes it again on load (lossy for the parts that were int4)")
-            w = torch.cat([dequantize_w4zp(*p) if isinstance(p, W4ZTensor) else p for p in parts], dim=0)
-        assert tuple(w.shape) == tuple(shape), f"{name}: {tuple(w.shape)} != {shape}"
-        yield name, shard_param(cfg, name, w, rank, tp)
+        quantized = [isinstance(p, W4ZTensor) for p in parts]
+        if w4a16 and any(quantized) and not all(quantized):
+            import warnings
+            warnings.warn(f"{name}: only some of {srcs} are quantized in the checkpoint; the packed matrix is dequantized and the "
+                          "w4a16 target quantizes it again on load (lossy for the parts that were int4)")
+        w = _assemble(cfg, name, shape, parts, "w4a16" if w4a16 else None, rank, tp, out_device)
+        yield name, (w4z_as_symmetric(w) if isinstance(w, W4ZTensor) else w)
 
 
 def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 1,
                      out_device: str | None = None, fp8: bool = False, w4a16: bool = False,
                      mxfp4: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
-    """Yields (name, bf16 tensor).  From a compressed-tensors fp8 checkpoint (checkpoint_quantization), a quantized decoder linear
-    comes as (name, (q float8_e4m3fn [N, K], s fp32 [N])) when ``fp8`` (the consumer is an fp8 target: no re-quantization) and as
-    bf16(s * q) otherwise.  Per-tensor scales of the packed q / k / v and gate / up are expanded to one per row before the packing;
-    input_scale tensors (activation quantization) are ignored; unquantized tensors (e.g. the LM head) load as bf16.
-    From a pack-quantized int4 checkpoint, a quantized linear comes as (name, W4Tensor(packed int32 [N, K/8], scale bf16 [N, K/128]))
-    when ``w4a16`` (codes and bf16 scales bit for bit; fp16 / fp32 scales are rounded to bf16 once) and as bf16(s * q), sharded as
-    usual, otherwise.  A W4A16 checkpoint into an fp8 target and an fp8 one into a W4A16 target are refused.
-    From an MXFP4 checkpoint, a quantized linear comes as (name, MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32])) when
-    ``mxfp4`` (codes and scale bytes bit for bit; scale bytes outside 2..252 are refused) and as the exact bf16 matrix
-    2^(b - 127) * e2m1(q), sharded as usual, otherwise.  MXFP4 checkpoints into fp8 / w4a16 targets and the reverse are refused.
-    From an AutoAWQ or GPTQ int4 checkpoint (_load_awq_gptq), a quantized linear comes as quant.W4ZTensor(packed, scale, zero) when
-    ``w4a16`` (a plain W4Tensor when all its zero points are 8) and as bf16(s * (u - z)) otherwise; fp8 and mxfp4 targets refuse it.
-    From a block-scaled fp8 checkpoint (fp8_block_scheme), a quantized linear comes as quant.FP8BTensor(codes, rowscale fp32
-    [N, ceil(K / 128)]) when ``fp8`` (codes bit for bit; every source tensor's weight_scale_inv expanded to one row of block scales
-    per output row, then concatenated) and as bf16(s * q), sharded as usual, otherwise; w4a16 and mxfp4 targets refuse it."""
-    from safetensors import safe_open
-    from ssd_amd.quant import FP8, dequantize_fp8, W4Tensor, dequantize_w4a16, MX4Tensor, dequantize_mxfp4, check_mxfp4_scales
-    from ssd_amd.quant import FP8_BLOCK, FP8BTensor, dequantize_fp8_block, expand_fp8_block_scales
+    """Yields (name, bf16 tensor), and for a quantized decoder linear of a quantized checkpoint (checkpoint_quantization) one of
+    the host forms of ssd_amd/quant.py instead when the consumer is a target of that kind (``fp8`` / ``w4a16`` / ``mxfp4``: codes and
+    scales bit for bit, no re-quantization; _assemble has the rule); a bf16 consumer gets the exact dequantized bf16 matrix, sharded
+    as usual, and a quantized target of another kind is refused before any tensor is read.  The forms, by checkpoint:
+      * compressed-tensors fp8: quant.FP8Tensor(q float8_e4m3fn [N, K], s fp32 [N]); per-tensor scales of q / k / v and gate / up are
+        expanded to one per row before the packing; input_scale tensors (activation quantization) are ignored;
+      * block-scaled fp8 (fp8_block_scheme): quant.FP8BTensor(codes, rowscale fp32 [N, ceil(K / 128)]), every source tensor's
+        weight_scale_inv expanded to one row of block scales per output row, then concatenated;
+      * pack-quantized int4: quant.W4Tensor(packed int32 [N, K/8], scale bf16 [N, K/128]); fp16 / fp32 scales are rounded to bf16 once;
+      * AutoAWQ / GPTQ int4 (_load_awq_gptq): quant.W4ZTensor(packed, scale, zero), a plain W4Tensor when all its zero points are 8;
+      * MXFP4: quant.MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32]); scale bytes outside 2..252 are refused.
+    Unquantized tensors (e.g. the LM head) load as bf16."""
+    from ssd_amd.quant import FP8, FP8Tensor, W4Tensor, MX4Tensor, check_mxfp4_scales, FP8_BLOCK, FP8BTensor, expand_fp8_block_scales
     assert fp8 + w4a16 + mxfp4 <= 1
+    target = "fp8" if fp8 else "w4a16" if w4a16 else "mxfp4" if mxfp4 else None
     qc = _quantization_config(model_dir)
     kind = _checkpoint_kind(qc)
     scheme = int4_checkpoint_scheme(qc)
+    if target is not None and kind is not None and kind != target:
+        what = f"{scheme['method']} int4" if scheme is not None else kind
+        raise ValueError(f"a checkpoint of the {what} kind cannot load into the {target} target: use quantization={kind!r} or None")
+    assert target is None or tp == 1, f"{target} targets are single-rank"
     if scheme is not None:
-        if fp8 or mxfp4:
-            raise ValueError(f"an {scheme['method']} int4 checkpoint cannot load into {'an fp8' if fp8 else 'an mxfp4'} target: use "
-                             "quantization='w4a16' or None")
-        assert not (w4a16 and tp > 1), "w4a16 targets are single-rank"
         yield from _load_awq_gptq(cfg, model_dir, scheme, rank, tp, out_device, w4a16)
         return
     ckpt_fp8 = kind == "fp8"
     block = fp8_block_scheme(qc)
-    if kind == "mxfp4" and (fp8 or w4a16):
-        raise ValueError(f"an mxfp4 checkpoint cannot load into {'an fp8' if fp8 else 'a w4a16'} target: use quantization='mxfp4' or None")
-    if kind in ("fp8", "w4a16") and mxfp4:
-        raise ValueError(f"{'an fp8' if kind == 'fp8' else 'an int4 (w4a16)'} checkpoint cannot load into an mxfp4 target: use "
-                         f"quantization={kind!r} or None")
-    if kind == "w4a16" and fp8:
-        raise ValueError("an int4 (w4a16) checkpoint cannot load into an fp8 target: use quantization='w4a16' or None")
-    if kind == "fp8" and w4a16:
-        raise ValueError("an fp8 checkpoint cannot load into a w4a16 target: use quantization='fp8' or None")
-    index: dict[str, str] = {}
-    for f in sorted(glob.glob(os.path.join(model_dir, "*.safetensors"))):
-        with safe_open(f, "pt", "cpu") as sf:
-            for k in sf.keys():
-                index[k] = f
+    index, raw = _safetensors_index(model_dir)
     if not block and any(k.endswith("weight_scale_inv") for k in index):
         raise ValueError("block-scaled fp8 checkpoints (weight_scale_inv) are not supported: use per-channel or per-tensor scales")
-    assert not (fp8 and tp > 1), "fp8 targets are single-rank"
-    assert not (w4a16 and tp > 1), "w4a16 targets are single-rank"
-    assert not (mxfp4 and tp > 1), "mxfp4 targets are single-rank"
     for k in index:
         if k.endswith(FP4_GLOBAL_SCALE_SUFFIX):
             raise ValueError(f"{k}: float-4 weights with a global scale tensor (NVFP4) are not supported; only MXFP4")
@@ -691,10 +690,6 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
             raise ValueError(f"{k}: asymmetric int4 weights (zero points) are not supported")
         if k.endswith("weight_g_idx"):
             raise ValueError(f"{k}: int4 weights with activation reordering (g_idx) are not supported")
-
-    def raw(name: str) -> torch.Tensor:
-        with safe_open(index[name], "pt", "cpu") as sf:
-            return sf.get_tensor(name)
 
     def get_w4(name: str) -> W4Tensor:
         base = name[:-len(".weight")]
@@ -744,12 +739,6 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
             raise ValueError(f"{sname} holds a scale that is not finite or not positive")
         return FP8BTensor(q.contiguous(), expand_fp8_block_scales(s, N))
 
-    def deq(p):
-        """bf16(s * q) of a pre-quantized fp8 part, per-row or block-scaled; anything else as it is."""
-        if isinstance(p, FP8BTensor):
-            return dequantize_fp8_block(*p)
-        return dequantize_fp8(*p) if isinstance(p, tuple) else p
-
     def get(name: str):
         if name not in index and name.endswith(".weight") and name[:-len(".weight")] + ".weight_packed" in index:
             return get_mx4(name) if kind == "mxfp4" else get_w4(name)
@@ -767,7 +756,7 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
                 s = s.reshape(N).contiguous()
             else:
                 raise ValueError(f"{name}_scale has shape {tuple(s.shape)}: expected a scalar or [{N}, 1]")
-            return t, s
+            return FP8Tensor(t, s)
         if t.dtype.is_floating_point and t.element_size() == 1:
             raise ValueError(f"{name} is {t.dtype}: only OCP float8_e4m3fn weights are supported (not fnuz / e5m2)")
         if not t.dtype.is_floating_point:
@@ -778,40 +767,4 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         srcs = _packed_sources(name)
         whole = name in index or name[:-len(".weight")] + ".weight_packed" in index
         parts = [get(s) for s in srcs] if srcs is not None and not whole else [get(name)]
-        if all(isinstance(p, MX4Tensor) for p in parts):
-            w = MX4Tensor(torch.cat([p.packed for p in parts], dim=0), torch.cat([p.scale for p in parts], dim=0))
-            if mxfp4:
-                assert (w.packed.shape[0], w.packed.shape[1] * 2) == tuple(shape), f"{name}: {tuple(w.packed.shape)} vs {shape}"
-                yield name, (MX4Tensor(w.packed.to(out_device), w.scale.to(out_device)) if out_device is not None else w)
-                continue
-            w = dequantize_mxfp4(*w)
-        elif any(isinstance(p, MX4Tensor) for p in parts):
-            w = torch.cat([dequantize_mxfp4(*p) if isinstance(p, MX4Tensor) else p for p in parts], dim=0)
-        elif all(isinstance(p, W4Tensor) for p in parts):
-            w = W4Tensor(torch.cat([p.packed for p in parts], dim=0), torch.cat([p.scale for p in parts], dim=0))
-            if not w4a16:
-                w = dequantize_w4a16(*w)
-            else:
-                assert (w.packed.shape[0], w.packed.shape[1] * 8) == tuple(shape), f"{name}: {tuple(w.packed.shape)} vs {shape}"
-                yield name, (W4Tensor(w.packed.to(out_device), w.scale.to(out_device)) if out_device is not None else w)
-                continue
-        elif any(isinstance(p, W4Tensor) for p in parts):
-            w = torch.cat([dequantize_w4a16(*p) if isinstance(p, W4Tensor) else p for p in parts], dim=0)
-        elif all(isinstance(p, FP8BTensor) for p in parts):
-            w = FP8BTensor(torch.cat([p.codes for p in parts], dim=0), torch.cat([p.rowscale for p in parts], dim=0))
-        elif all(isinstance(p, tuple) for p in parts) and not any(isinstance(p, FP8BTensor) for p in parts):
-            w = (torch.cat([p[0] for p in parts], dim=0), torch.cat([p[1] for p in parts], dim=0))
-        else:
-            w = torch.cat([deq(p) for p in parts], dim=0)
-        if isinstance(w, tuple) and not fp8:
-            w = deq(w)
-        got = tuple(w[0].shape if isinstance(w, tuple) else w.shape)
-        assert got == tuple(shape), f"{name}: {got} != {shape}"
-        if isinstance(w, tuple):
-            if out_device is not None:
-                moved = (w[0].to(out_device), w[1].to(out_device))
-                w = FP8BTensor(*moved) if isinstance(w, FP8BTensor) else moved
-            yield name, w
-            continue
-        w = shard_param(cfg, name, w, rank, tp)
-        yield name, (w.to(out_device) if out_device is not None else w)
+        yield name, _assemble(cfg, name, shape, parts, target, rank, tp, out_device)

@@ -5,7 +5,7 @@ The host side of the decoder decides which kernels a forward launches, with whic
 mode, quantized target, KV cache format, tensor parallelism and the EAGLE-3 draft; a change there that is meant to leave behaviour
 alone must reproduce the recording entry for entry.  No GPU: the decoder is built on torch.device("meta") at the full width of a
 preset (three layers), its weights are torch.empty placeholders under the names and shapes of weights.param_shapes (+ "_scale" /
-"_zero" tables), and every launching function of the op modules is replaced by a recorder.  The host-side queries (REAL below) stay
+"_zero" / "_bscale" tables), and every launching function of the op modules is replaced by a recorder.  The host-side queries (REAL below) stay
 real, so the built library is needed.
 
 An entry is the function and its arguments BOUND TO ITS SIGNATURE, arguments that equal their default left out: passing a default
@@ -14,7 +14,7 @@ AttnMeta field or scenario input that owns its storage (what _base answers for a
 dtype, whose _base is an intermediate) -- plus storage offset, dtype and shape: buf_h and buf_res have the same shape and swapping them
 fails; kv_cache[li, 0 | 1] and the residual ping-pong show up per layer.
 
-The recording is written by this file's own record mode,
+The recording (two files: FIXTURE, and FIXTURE_MORE for the scenarios added since) is written by this file's own record mode,
 
     python tests/test_decoder_trace_cpu.py --record [--commit HASH]
 
@@ -34,18 +34,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 FIXTURE = os.path.join(ROOT, "tests", "golden", "decoder_trace.json")
+# scenarios added after the first recording (spec more=True) are kept in a file of their own: a recording is one line of JSON, so
+# extending the first file would rewrite all of it, and this way the first recording stays byte for byte what it was
+FIXTURE_MORE = os.path.join(ROOT, "tests", "golden", "decoder_trace_more.json")
 
 META = torch.device("meta")
 BF16 = torch.bfloat16
-OP_MODULES = ("ops", "quant_ops", "w4_ops", "w4zp_ops", "mx4_ops", "kv8_ops")
+OP_MODULES = ("ops", "quant_ops", "fp8b_ops", "w4_ops", "w4zp_ops", "mx4_ops", "kv8_ops", "lora_ops")
 # host-side queries: they launch nothing and keep their real implementation (and are not recorded)
 REAL = {"frag_numel", "gemm_pf_workspace_bytes", "gemm_argmax_nparts", "chain_segment_ok", "chain_granule_bytes", "tree_segment_ok",
         "tree_segment_workspace_bytes", "fork_topf_workspace_bytes"}
 AR_METHODS = ("fits", "fits_rows", "all_reduce", "all_reduce_add_rmsnorm", "all_gather_words")
 REQUIRED = {"chain_segment", "tree_segment", "gemm_parts", "rmsnorm_parts", "attn_oproj_parts", "rope_store_kv_parts",
             "gemm_pf", "gemm_fused", "gemm_argmax", "argmax_parts", "argmax_rows", "argmax_rows_val", "argmax_merge", "rmsnorm_pair",
-            "gemm_fp8", "gemm_w4a16", "gemm_w4a16_zp", "gemm_mxfp4",
-            "fp8_dequant_frag", "w4_dequant_frag", "w4zp_dequant_frag", "mx4_dequant_frag",
+            "gemm_fp8", "gemm_fp8b", "gemm_w4a16", "gemm_w4a16_zp", "gemm_mxfp4",
+            "fp8_dequant_frag", "fp8b_dequant_frag", "w4_dequant_frag", "w4zp_dequant_frag", "mx4_dequant_frag",
+            "lora_shrink", "lora_expand",
             "rope_store_kv_fp8", "attn_paged_fp8", "all_reduce_add_rmsnorm", "all_gather_words"}
 MIN_CALLS = 8
 
@@ -99,6 +103,13 @@ def _scenarios() -> dict:
             S[f"bench/{p}-M{M}"] = dict(preset=p, T=M, kind="bench")
     for T in (1, 8, 40, 300):
         S[f"eagle/eagle3-llama-3.1-8b-T{T}"] = dict(preset="eagle3-llama-3.1-8b", T=T, B=1, ctx=1024, kind="eagle")
+    for T in (8, 100, 300):
+        S[f"quant/fp8b-llama-3.1-8b-T{T}"] = dict(preset="llama-3.1-8b", T=T, B=1, ctx=1024, dec=dict(quantization="fp8"), bscale=True,
+                                                      more=True)
+    for tag, kw in (("bf16", {}), ("w4a16", dict(quantization="w4a16"))):
+        for T in (8, 100, 300):
+            S[f"lora/{tag}-llama-3.1-8b-T{T}"] = dict(preset="llama-3.1-8b", T=T, B=1, ctx=1024, dec=dict(max_loras=2, **kw), lora=True,
+                                                            more=True)
     return S
 
 
@@ -137,7 +148,9 @@ def build_decoder(spec: dict):
         if dec.quantized and quant.is_quantized_linear(name):
             N, K = t.shape
             dec.w[name] = _empty(N, K, dtype=torch.uint8)
-            if dec.fp8:
+            if dec.fp8 and spec.get("bscale") and ("qkv_proj" in name or "down_proj" in name):     # block scales on half the linears
+                dec.w[name + "_bscale"] = _empty(N // 16, -(-K // quant.FP8_BLOCK), dtype=torch.float32)
+            elif dec.fp8:
                 dec.w[name + "_scale"] = _empty(N, dtype=torch.float32)
             elif dec.w4:
                 dec.w[name + "_scale"] = _empty(N, K // quant.W4_GROUP)
@@ -286,6 +299,9 @@ def run_scenario(name: str) -> list[tuple[str, ...]]:
         inp.update(out=_empty(n, dtype=torch.int64), out2=_empty(n, dtype=torch.int64), out3=_empty(n, 3, dtype=torch.int64),
                    gather=i32(B), acts_rows=_empty(T, getattr(dec, "A", 1)))
         rec.name("{}", inp), rec.name("meta.{}", meta), rec.name("w[{}]", dec.w), rec.name("{}", dec)
+        if spec.get("lora"):        # an adapted row in the batch: every linear takes the ROWS route and adds its delta
+            dec.lora_active = True
+            rec.name("lora_a[{}]", dec.lora_a), rec.name("lora_b[{}]", dec.lora_b)
         if kind == "eagle":
             dec.project(inp["acts_rows"], T, dec.buf_cond)
         dec.forward(inp["input_ids"], inp["positions"], T, meta)
@@ -308,27 +324,31 @@ def _show(entry) -> str:
 
 @pytest.fixture(scope="module")
 def recorded():
-    with open(FIXTURE) as f:
-        fx = json.load(f)
-    atoms = fx["atoms"]
-    fx["decoded"] = [tuple(atoms[i] for i in e) for e in fx["entries"]]
-    return fx
+    """name -> the recorded entries of every scenario, from both files."""
+    out = {}
+    for path, more in ((FIXTURE, False), (FIXTURE_MORE, True)):
+        with open(path) as f:
+            fx = json.load(f)
+        decoded = [tuple(fx["atoms"][i] for i in e) for e in fx["entries"]]
+        assert set(fx["scenarios"]) == {n for n, spec in SCENARIOS.items() if bool(spec.get("more")) == more}, path
+        out.update({name: [decoded[i] for i in idx] for name, idx in fx["scenarios"].items()})
+    return out
 
 
 def test_recording_is_not_hollow(recorded):
-    assert os.path.getsize(FIXTURE) < 1 << 20
-    assert set(recorded["scenarios"]) == set(SCENARIOS)
+    assert os.path.getsize(FIXTURE) < 1 << 20 and os.path.getsize(FIXTURE_MORE) < 1 << 20
+    assert set(recorded) == set(SCENARIOS)
     seen = set()
-    for name, idx in recorded["scenarios"].items():
-        assert len(idx) >= MIN_CALLS, f"{name}: only {len(idx)} calls recorded"
-        seen.update(recorded["decoded"][i][0].split(".", 1)[1] for i in idx)
+    for name, entries in recorded.items():
+        assert len(entries) >= MIN_CALLS, f"{name}: only {len(entries)} calls recorded"
+        seen.update(e[0].split(".", 1)[1] for e in entries)
     assert not REQUIRED - seen, f"never recorded: {sorted(REQUIRED - seen)}"
 
 
 @pytest.mark.parametrize("group", GROUPS)
 def test_decoder_launches_are_the_recorded_ones(recorded, group):
     for name in (n for n in SCENARIOS if n.split("/")[0] == group):
-        want = [recorded["decoded"][i] for i in recorded["scenarios"][name]]
+        want = recorded[name]
         got = run_scenario(name)
         for i, (a, b) in enumerate(zip(got, want)):
             assert a == b, (f"{name}: call {i} differs from the recording\n  got      {_show(a)}\n  recorded {_show(b)}\n"
@@ -337,32 +357,34 @@ def test_decoder_launches_are_the_recorded_ones(recorded, group):
 
 
 def record(commit: str) -> None:
-    """Run every scenario twice (the two recordings must agree) and write the fixture: a table of distinct strings, a table of distinct
-    entries as indices into it, and one index list per scenario."""
-    atoms, atom_ix, entries, entry_ix, scenarios = [], {}, [], {}, {}
-    for name in SCENARIOS:
-        a, b = run_scenario(name), run_scenario(name)
-        assert a == b, f"{name}: the two recordings differ"
-        assert len(a) >= MIN_CALLS, f"{name}: only {len(a)} calls"
-        out = []
-        for e in a:
-            if e not in entry_ix:
-                for s in e:
-                    if s not in atom_ix:
-                        atom_ix[s] = len(atoms)
-                        atoms.append(s)
-                entry_ix[e] = len(entries)
-                entries.append([atom_ix[s] for s in e])
-            out.append(entry_ix[e])
-        scenarios[name] = out
-    seen = {e[0].split(".", 1)[1] for e in entry_ix}
+    """Run every scenario twice (the two recordings must agree) and write the two fixtures, each a table of distinct strings, a
+    table of distinct entries as indices into it, and one index list per scenario of its own."""
+    seen = set()
+    first = os.environ.get("DECODER_TRACE_OUT", FIXTURE)
+    for out, more in ((first, False), (first[:-len(".json")] + "_more.json", True)):
+        atoms, atom_ix, entries, entry_ix, scenarios = [], {}, [], {}, {}
+        for name in (n for n, spec in SCENARIOS.items() if bool(spec.get("more")) == more):
+            a, b = run_scenario(name), run_scenario(name)
+            assert a == b, f"{name}: the two recordings differ"
+            assert len(a) >= MIN_CALLS, f"{name}: only {len(a)} calls"
+            idx = []
+            for e in a:
+                if e not in entry_ix:
+                    for s in e:
+                        if s not in atom_ix:
+                            atom_ix[s] = len(atoms)
+                            atoms.append(s)
+                    entry_ix[e] = len(entries)
+                    entries.append([atom_ix[s] for s in e])
+                idx.append(entry_ix[e])
+            scenarios[name] = idx
+        seen |= {e[0].split(".", 1)[1] for e in entry_ix}
+        with open(out, "w") as f:
+            json.dump({"recorded_at": commit, "atoms": atoms, "entries": entries, "scenarios": scenarios}, f, separators=(",", ":"))
+            f.write("\n")
+        print(f"wrote {out}: {len(scenarios)} scenarios, {sum(map(len, scenarios.values()))} calls, {len(entries)} distinct entries, "
+              f"{len(atoms)} distinct strings, {os.path.getsize(out)} bytes")
     assert not REQUIRED - seen, f"never reached: {sorted(REQUIRED - seen)}"
-    out = os.environ.get("DECODER_TRACE_OUT", FIXTURE)
-    with open(out, "w") as f:
-        json.dump({"recorded_at": commit, "atoms": atoms, "entries": entries, "scenarios": scenarios}, f, separators=(",", ":"))
-        f.write("\n")
-    print(f"wrote {out}: {len(scenarios)} scenarios, {sum(map(len, scenarios.values()))} calls, {len(entries)} distinct entries, "
-          f"{len(atoms)} distinct strings, {os.path.getsize(out)} bytes")
 
 
 if __name__ == "__main__":

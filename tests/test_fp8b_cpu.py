@@ -175,6 +175,28 @@ def test_decoders_of_other_formats_refuse_block_tensors():
             dec.load_weights(iter([(P + "self_attn.o_proj.weight", w)]))
 
 
+FOREIGN = [(kind, host) for kind, hosts in (("fp8", ("W4Tensor", "W4ZTensor", "MX4Tensor")),
+                                            ("w4a16", ("FP8Tensor", "FP8BTensor", "MX4Tensor")),
+                                            ("mxfp4", ("FP8Tensor", "FP8BTensor", "W4Tensor", "W4ZTensor"))) for host in hosts]
+
+
+@pytest.mark.parametrize("kind,host", FOREIGN)
+def test_every_quantized_decoder_refuses_every_host_form_of_another_kind(kind, host):
+    """The whole matrix, not only the block-scaled column above: a ValueError that names the tensor's format and the decoder's."""
+    from ssd_amd import quant
+    from ssd_amd.model import HipDecoder
+    make = {"FP8Tensor": quant.quantize_fp8, "FP8BTensor": quant.quantize_fp8_block, "W4Tensor": quant.quantize_w4a16,
+            "W4ZTensor": quant.quantize_w4a16_zp, "MX4Tensor": quant.quantize_mxfp4}[host]
+    phrase = {"FP8Tensor": "per-row fp8", "FP8BTensor": "block-scaled fp8", "W4Tensor": "int4", "W4ZTensor": "zero-point int4",
+              "MX4Tensor": "MXFP4"}[host]
+    w = make((0.02 * torch.randn(128, 128)).to(torch.bfloat16))
+    dec = HipDecoder.__new__(HipDecoder)
+    dec.fp8, dec.mx4, dec.w4, dec.quantized, dec.device = kind == "fp8", kind == "mxfp4", kind == "w4a16", True, torch.device("cpu")
+    with pytest.raises(ValueError) as e:
+        dec.load_weights(iter([(P + "self_attn.o_proj.weight", w)]))
+    assert phrase in str(e.value) and kind in str(e.value), str(e.value)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The group table
 # ---------------------------------------------------------------------------------------------------------------------
