@@ -96,6 +96,26 @@ class Config:
     max_loras: int = 4
     max_lora_rank: int = 64
 
+    def _check_moe_target(self) -> None:
+        """A Qwen3-MoE target (hf_config.num_experts > 0) runs bf16 experts on one GPU: everything else is refused by parameter."""
+        what = f"a mixture-of-experts target ({self.hf_config.num_experts} experts)"
+        if self.quantization is not None:
+            raise ValueError(f"quantization={self.quantization!r} is not supported with {what}: the expert tables are bf16 only")
+        if self.kv_cache_dtype is not None:
+            raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r} is not supported with {what}")
+        if self.enable_lora:
+            raise ValueError(f"enable_lora=True is not supported with {what}")
+        if self.num_gpus > 1 and not (self.speculate and self.draft_async and self.num_gpus - self.num_draft_gpus == 1):
+            raise ValueError(f"num_gpus={self.num_gpus} is not supported with {what}: no tensor or expert parallelism (the target runs "
+                             "on one GPU; an asynchronous draft may have its own)")
+        if self.use_eagle:
+            raise ValueError(f"use_eagle=True is not supported with {what} (EAGLE-3 taps need the dense bf16 target path)")
+        c = self.hf_config
+        if not (1 <= c.num_experts_per_tok <= 8 <= c.num_experts <= 256) or c.num_experts % 8 or c.moe_intermediate_size % 32 or c.moe_intermediate_size <= 0:
+            raise ValueError(f"unsupported expert geometry: num_experts={c.num_experts} (8..256, a multiple of 8), "
+                             f"num_experts_per_tok={c.num_experts_per_tok} (1..8), moe_intermediate_size={c.moe_intermediate_size} "
+                             "(a multiple of 32)")
+
     @property
     def max_blocks(self) -> int:
         return -(-self.max_model_len // self.kvcache_block_size)
@@ -137,10 +157,15 @@ class Config:
         if self.hf_config is None:
             self.hf_config = resolve_model_config(self.model)
         self.max_model_len = min(self.max_model_len, self.hf_config.max_position_embeddings)
+        if self.hf_config.num_experts > 0:
+            self._check_moe_target()
         if self.speculate:
             assert self.draft is not None, "speculate=True needs a draft model"
             if self.draft_hf_config is None:
                 self.draft_hf_config = resolve_model_config(self.draft)
+            if self.draft_hf_config.num_experts > 0:
+                raise ValueError(f"draft={self.draft!r} is a mixture-of-experts model ({self.draft_hf_config.num_experts} experts): MoE "
+                                 "drafts are not supported, only MoE targets")
             self.max_model_len = min(self.max_model_len, self.draft_hf_config.max_position_embeddings)
             assert self.draft_hf_config.vocab_size == self.hf_config.vocab_size, "draft and target vocab must match"
             if self.use_eagle:

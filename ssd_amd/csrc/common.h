@@ -31,6 +31,7 @@ constexpr int SSD_MAX_DEVICES = 16;  // per-device host-side caches (function at
 #include "ssd_hip_guide.h"
 #include "ssd_hip_prompt_logprob.h"
 #include "ssd_hip_lora.h"
+#include "ssd_hip_moe.h"
 
 __device__ __forceinline__ float bf2f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
 

@@ -96,6 +96,10 @@ class LLMEngine:
         from ssd_amd.utils import watchdog
         watchdog.stage("runner_init (weights, KV cache, buffers)")
         factory = runner_factory or hip_runner_factory
+        moe = config.hf_config.num_experts > 0
+        if moe and self.topo.device.type != "cuda":
+            raise ValueError(f"model={model!r} is a mixture-of-experts target: it needs the HIP runner on a GPU (there is no CPU oracle "
+                             "for the family)")
 
         self.draft_runner = None
         self.loras = None           # enable_lora: the registry of the adapter slots (ssd_amd/lora.py), else None
@@ -122,6 +126,8 @@ class LLMEngine:
             return
         self.model_runner = factory(config, config.hf_config, is_draft=False, topo=self.topo,
                                     num_kvcache_blocks=config.num_kvcache_blocks)
+        if moe and not getattr(self.model_runner, "supports_moe", False):
+            raise ValueError(f"model={model!r} is a mixture-of-experts target: {type(self.model_runner).__name__} has no expert kernels")
         config.num_kvcache_blocks = self.model_runner.num_kvcache_blocks
         draft_blocks = None
         if config.speculate and not config.draft_async:

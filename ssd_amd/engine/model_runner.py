@@ -73,6 +73,7 @@ class ModelRunner:
     supports_logit_constraints = True   # min_tokens / allowed_token_ids / bad_words_ids (csrc/constrain.hip); likewise
     supports_guided_decoding = True     # guided_automaton / guided_choice_ids (csrc/guide.hip); likewise
     supports_lora = True                # SamplingParams(lora=name): per-row adapter deltas on the target (csrc/lora.hip); likewise
+    supports_moe = True                 # Qwen3-MoE targets (csrc/moe.hip); LLMEngine refuses them on runners without it
     PENALTY_MAX_BIAS = Penalties.MAX_BIAS       # logit_bias entries one request may carry
 
     PROMPT_LOGPROB_ROWS = 512       # default of prompt_logprob_rows: the fastest of 128 / 256 / 512 per prompt row ("Prompt log-probabilities")

@@ -28,6 +28,7 @@ from ssd_amd.hip import w4zp_ops as W4Z
 from ssd_amd.hip import mx4_ops as MX4
 from ssd_amd.hip import kv8_ops as KV8
 from ssd_amd.hip import lora_ops as LO
+from ssd_amd.hip import moe_ops as MOE
 from ssd_amd import lora as LR
 from ssd_amd import quant
 from ssd_amd.model_config import ModelConfig
@@ -82,6 +83,14 @@ class HipDecoder:
                  taps: list[int] | None = None, quantization: str | None = None, w4_zero_point: bool = False,
                  kv_cache_dtype: str | None = None, max_loras: int = 0, max_lora_rank: int = 64):
         self.cfg, self.device = cfg, device
+        # cfg.num_experts > 0 (Qwen3-MoE): the MLP of every layer is a router + routed experts (include/ssd_hip_moe.h).  The decoder
+        # takes the ROWS route exactly as a quantized target does -- every fused form off -- and launch_gate_up / launch_down, the only
+        # two places the MLP lives, run add + norm (rows and frag), router GEMM, route, grouped up GEMM | grouped down GEMM, combine.
+        # bf16 tables, bf16 KV, one rank, no adapters, no taps (Config refuses the rest by name).
+        self.moe = cfg.num_experts > 0
+        self.moe_trace: list | None = None      # debug hook: a list -> every eager MoE layer appends (router_logits.cpu(), topk_ids.cpu())
+        assert not self.moe or (tp_size == 1 and not force_collectives and taps is None and quantization is None
+                                and kv_cache_dtype is None and max_loras == 0), "MoE targets are single-rank bf16, without taps or adapters"
         # max_loras > 0 (Config.enable_lora): slot tables of LoRA adapters for the four linears of every layer (include/ssd_hip_lora.h,
         # ssd_amd/lora.py), allocated once at the end of __init__ -- before the KV cache is sized, so their memory is counted.  A
         # forward whose batch has an adapted row (lora_active, set by the runner with the row_slot array) takes the ROWS route of
@@ -129,7 +138,7 @@ class HipDecoder:
         assert cfg.intermediate_size % (tp_size * 32) == 0 and cfg.vocab_size % (tp_size * 16) == 0
         self.nh, self.nkv = cfg.num_heads // tp_size, cfg.num_kv_heads // tp_size
         self.hd, self.h = cfg.head_dim, cfg.hidden_size
-        self.I = cfg.intermediate_size // tp_size
+        self.I = cfg.moe_intermediate_size if self.moe else cfg.intermediate_size // tp_size
         self.V = cfg.vocab_size // tp_size
         self.qkv_n = (self.nh + 2 * self.nkv) * self.hd
         self.qn = self.nh * self.hd
@@ -178,7 +187,7 @@ class HipDecoder:
             self.use_parts = False
         self.fuse_attn_o = True
         self.pf_parts = True
-        if self.quantized:
+        if self.quantized or self.moe:
             self.use_parts = self.fuse_attn_o = self.pf_parts = False
         if self.kv8:
             self.fuse_attn_o = False
@@ -195,7 +204,7 @@ class HipDecoder:
         _geo = (self.h, self.qn, self.I, self.qkv_n, self.hd)
         _validated = _geo == (2048, 2048, 8192, 3072, 64)
         self.chain_seg = ((_cs == "1" or (_cs == "auto" and _validated)) and not cfg.qk_norm and tp_size == 1 and not self.use_coll and not self.quantized
-                          and not self.kv8 and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
+                          and not self.moe and not self.kv8 and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         # the same segment for 2..30 token rows (csrc/tree_segment.hip): attention + ONE resident launch per layer instead of 7
         # launches.  Measured on MI355X at the 1B draft's geometry (profiles/r05_tree_seg_probe_v1.txt, parity tests/test_hip_tree_segment.py):
         # the K+1 = 8-row glue decode 0.945 -> 0.857 ms (kept), the 24-row tree step 0.943 -> 0.965 ms (NOT kept: at 24 rows every
@@ -211,7 +220,7 @@ class HipDecoder:
         #  is all there is: tree step 1.248 -> 1.240 ms at 6 rows, 1.275 -> 1.299 at 12, 1.363 -> 1.457 at 24,
         #  profiles/r05_tree_seg_probe_qwen.txt -- so "auto" leaves it off there)
         self.tree_seg = ((_ts == "1" or (_ts == "auto" and _validated)) and tp_size == 1 and not self.use_coll and not self.quantized
-                         and not self.kv8 and taps is None and max_tokens >= 2
+                         and not self.moe and not self.kv8 and taps is None and max_tokens >= 2
                          and H.tree_segment_ok(2, self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         if self.chain_seg:
             self.chain_gr = z(H.chain_granule_bytes(self.h, self.I) // 8, dtype=torch.int64)
@@ -235,6 +244,9 @@ class HipDecoder:
         # fp32 split-K partials of the prefill GEMM (csrc/gemm_pf.hip), sized ONCE for the largest matrix that can take that
         # path (layer matrices and the LM head): prefill hipGraphs bake this pointer, so it must never be reallocated
         pf_shapes = [(self.qkv_n, self.h), (self.h, self.qn), (2 * self.I, self.h), (self.h, self.I), (self.V, self.h)]
+        if self.moe:        # the router is the one MLP matrix of a MoE layer that runs on the dense GEMMs
+            self.moe_En = -(-cfg.num_experts // 16) * 16        # its rows padded to whole 16-row groups (zero rows: logits never read)
+            pf_shapes[2:4] = [(self.moe_En, self.h)]
         need = max([H.gemm_pf_workspace_bytes(128, n, k) // 4 for n, k in pf_shapes if self._pf_eligible(n, k)], default=0)
         # a whole prompt of >= LM_MIN_TOKENS rows is one gemm_pf launch per linear, whatever the matrix size; the query at
         # max_tokens covers every shorter prompt (0 where no decomposition splits K)
@@ -272,6 +284,67 @@ class HipDecoder:
         self.am_pack = z(tp_size, self.am_words, dtype=torch.int64)
         if max_loras:
             self._alloc_lora(z)
+        if self.moe:
+            self._alloc_moe(z)
+
+    # ---- routed experts ------------------------------------------------------------------------------
+    def _alloc_moe(self, z) -> None:
+        """Everything a MoE layer writes between its norm and the combine, once (hipGraphs bake the pointers): the normed rows (the
+        grouped GEMM gathers row-major x), the router-logit rows, the route tables, and act / d by entry (entry = token * k + choice)."""
+        cfg, T = self.cfg, self.max_tokens
+        E, k = cfg.num_experts, cfg.num_experts_per_tok
+        self.moe_x = z(T, self.h)
+        self.moe_logits = z(T, self.moe_En)
+        self.moe_ids = z(T * k, dtype=torch.int32)
+        self.moe_w = z(T * k, dtype=torch.float32)
+        self.moe_offs = z(E + 1, dtype=torch.int32)
+        self.moe_perm = z(T * k, dtype=torch.int32)
+        self.moe_act = z(T * k, self.I)
+        self.moe_d = z(T * k, self.h)
+
+    def _load_moe(self, name: str, w: torch.Tensor) -> bool:
+        """The three tensors of a MoE layer's MLP -> their device tables; False for any other name."""
+        from ssd_amd.weights import MOE_GATE, MOE_GATE_UP, MOE_DOWN
+        E = self.cfg.num_experts
+        if name.endswith(MOE_GATE):             # the router: fragment-major, zero rows up to a whole 16-row group
+            assert tuple(w.shape) == (E, self.h), (name, tuple(w.shape))
+            pad = torch.zeros(self.moe_En, self.h, dtype=BF16, device=self.device)
+            pad[:E] = w
+            out = torch.empty(self.moe_En * self.h, dtype=BF16, device=self.device)
+            H.rows_to_frag(pad, out, self.moe_En, self.h)
+        elif name.endswith(MOE_GATE_UP) or name.endswith(MOE_DOWN):
+            # E matrices, one after the other, each fragment-major; gate_up with gate / up 16-row groups interleaved (mode 1)
+            up = name.endswith(MOE_GATE_UP)
+            N, K = (2 * self.I, self.h) if up else (self.h, self.I)
+            assert tuple(w.shape) == (E, N, K), (name, tuple(w.shape))
+            out = torch.empty(E * N * K, dtype=BF16, device=self.device)
+            for e in range(E):
+                H.rows_to_frag(w[e], out[e * N * K:(e + 1) * N * K], N, K, mode=1 if up else 0)
+        else:
+            return False
+        self.w[name] = out
+        return True
+
+    def _moe_up(self, li: int, T: int) -> None:
+        """The normed rows are in moe_x (rows) and buf_xf (frag): router GEMM -> route -> grouped gate_up GEMM with SiLU * mul."""
+        from ssd_amd.weights import MOE_GATE, MOE_GATE_UP
+        cfg, p = self.cfg, f"model.layers.{li}."
+        E, k = cfg.num_experts, cfg.num_experts_per_tok
+        self._gemm(self.buf_xf, self.h, self.w[p + MOE_GATE], self.moe_En, self.moe_logits, T, self.moe_En)
+        MOE.moe_route(self.moe_logits, self.moe_En, T, E, k, cfg.norm_topk_prob, self.moe_ids, self.moe_w, self.moe_offs, self.moe_perm)
+        if self.moe_trace is not None:
+            self.moe_trace.append((self.moe_logits[:T, :E].cpu(), self.moe_ids[:T * k].view(T, k).cpu()))
+        MOE.moe_gemm(self.moe_x, self.w[p + MOE_GATE_UP], self.moe_offs, self.moe_perm, self.moe_act, T, k, E, 2 * self.I, self.h,
+                     MOE.EPI_UP)
+
+    def _moe_down(self, li: int, T: int) -> None:
+        """Grouped down GEMM of moe_act -> moe_d by entry, then the weighted combine into buf_h (rows: the hand-off None)."""
+        from ssd_amd.weights import MOE_DOWN
+        cfg = self.cfg
+        E, k = cfg.num_experts, cfg.num_experts_per_tok
+        MOE.moe_gemm(self.moe_act, self.w[f"model.layers.{li}." + MOE_DOWN], self.moe_offs, self.moe_perm, self.moe_d, T, k, E, self.h,
+                     self.I, MOE.EPI_DOWN)
+        MOE.moe_combine(self.moe_d, self.moe_w, self.buf_h, T, k, self.h)
 
     # ---- LoRA adapters -----------------------------------------------------------------------------
     LORA_SPLIT_MAX_T = 256      # forwards of up to this many rows split the shrink's K over the default number of workgroups; longer
@@ -350,6 +423,8 @@ class HipDecoder:
             if quant.is_prequantized(w):        # a bf16 decoder (or a matrix that stays bf16) computes with bf16(s * q)
                 w = quant.to_device(w, self.device).dequantize()
             w = w.to(self.device).contiguous()
+            if self.moe and self._load_moe(name, w):
+                continue
             if name.endswith("qkv_proj.weight"):
                 # rotation-paired row order: RoPE pairs share an accumulator tile (fused epilogue) -- layout.hip
                 out = torch.empty(w.numel(), dtype=BF16, device=self.device)
@@ -696,7 +771,7 @@ class HipDecoder:
         between producer and norm: the prologue is paid by EVERY workgroup and its LDS image limits residency --
         measured on MI355X, M=7 x K=4096 made gate_up 73 us vs 49 us unfused, M=1 x K=2048 made norm+qkv+rope 5.6 us
         vs 14.8 us."""
-        small = T <= 16 and not self.cfg.qk_norm and not self.quantized and not self.kv8
+        small = T <= 16 and not self.cfg.qk_norm and not self.quantized and not self.kv8 and not self.moe
         return small, small and not self.use_coll and T * self.h // 8 <= 1024
 
     def chain_plan(self, T: int, meta: AttnMeta, splits: int) -> bool:
@@ -850,6 +925,9 @@ class HipDecoder:
         parts_plan says), or None for rows in buf_h."""
         name, xf, K, slabs = ((f"model.layers.{li}.self_attn.o_proj.weight", self.buf_af, self.qn, self.buf_parts_o) if which == "o" else
                               (f"model.layers.{li}.mlp.down_proj.weight", self.buf_actf, self.I, self.buf_parts_d))
+        if which == "d" and self.moe:
+            self._moe_down(li, T)
+            return None
         w = self.w[name]
         if self.lora_active:        # rows into buf_h, then the delta: no slabs of any kind
             self._gemm(xf, K, name, self.h, self.buf_h, T, self.h)
@@ -873,6 +951,12 @@ class HipDecoder:
         p = f"model.layers.{li}."
         if src is _PLAN:
             src = self._plan_src("o", T)
+        if self.moe:
+            if not gemm_only:
+                self._add_norm(src, T, w[p + "post_attention_layernorm.weight"], res_in=self.buf_res, res_out=self.buf_res,
+                               out_rows=self.moe_x, out_frag=self.buf_xf)
+            self._moe_up(li, T)
+            return
         if self.lora_active:        # rows in the packed gate / up order -> delta -> SiLU * mul of the updated rows, fragment-major
             if not gemm_only:
                 self._add_norm(src, T, w[p + "post_attention_layernorm.weight"], res_in=self.buf_res, res_out=self.buf_res, out_frag=self.buf_xf)

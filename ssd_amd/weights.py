@@ -5,6 +5,9 @@ Parameter names are the reference's packed names (ssd/models/llama3.py:277-283, 
   [(nh+2nkv)hd, h] (+ .bias, + q_norm/k_norm for Qwen3); .self_attn.o_proj.weight [h, nh*hd];
   .post_attention_layernorm.weight; .mlp.gate_up_proj.weight [2I, h]; .mlp.down_proj.weight [h, I];
   model.norm.weight; lm_head.weight [V,h] (absent when tied).
+A Qwen3-MoE layer (cfg.num_experts > 0) has, in place of the two MLP matrices, .mlp.gate.weight [E,h] (the router),
+.mlp.experts.gate_up_proj [E,2I,h] (every expert's [gate ; up] halves) and .mlp.experts.down_proj [E,h,I] -- the fused names
+transformers keeps in memory.
 Sharding follows the reference weight loaders (ssd/layers/linear.py:90-95,116-122,148-162,188-193;
 ssd/layers/embed_head.py:41-47).
 
@@ -45,6 +48,10 @@ def eagle_param_shapes(cfg: ModelConfig) -> list[tuple[str, tuple[int, ...]]]:
             ("d2t", (cfg.draft_vocab_size,))]
 
 
+# Qwen3-MoE parameter names below "model.layers.{i}." (transformers' Qwen3MoeSparseMoeBlock: the router, and the experts fused 3-D)
+MOE_GATE, MOE_GATE_UP, MOE_DOWN = "mlp.gate.weight", "mlp.experts.gate_up_proj", "mlp.experts.down_proj"
+
+
 def param_shapes(cfg: ModelConfig) -> list[tuple[str, tuple[int, ...]]]:
     if cfg.family == "eagle3":
         return eagle_param_shapes(cfg)
@@ -61,6 +68,12 @@ def param_shapes(cfg: ModelConfig) -> list[tuple[str, tuple[int, ...]]]:
             out.append((p + "self_attn.k_norm.weight", (hd,)))
         out.append((p + "self_attn.o_proj.weight", (h, nh * hd)))
         out.append((p + "post_attention_layernorm.weight", (h,)))
+        if cfg.num_experts > 0:
+            E, Im = cfg.num_experts, cfg.moe_intermediate_size
+            out.append((p + MOE_GATE, (E, h)))
+            out.append((p + MOE_GATE_UP, (E, 2 * Im, h)))
+            out.append((p + MOE_DOWN, (E, h, Im)))
+            continue
         out.append((p + "mlp.gate_up_proj.weight", (2 * I, h)))
         out.append((p + "mlp.down_proj.weight", (h, I)))
     out.append(("model.norm.weight", (h,)))
@@ -265,6 +278,10 @@ def synthetic_tensor(name: str, shape, seed: int, std: float, gen_device: str, n
             return torch.ones(shape, dtype=BF16, device=gen_device)
         return (1.0 + norm_jitter * torch.randn(shape, generator=g, device=gen_device, dtype=torch.float32)).to(BF16)
     t = std * torch.randn(shape, generator=g, device=gen_device, dtype=torch.float32)
+    if recipe is not None and name.endswith(MOE_GATE):
+        # router_gain (any recipe kind): a multiple of the synthetic router matrix, i.e. of every router logit -- random routers
+        # decide by margins of a few bf16 ulps, and a test that compares routes needs them wide
+        t = t * float(recipe.get("router_gain", 1.0))
     if recipe is not None and recipe.get("kind") == "peaky" and name == "lm_head.weight":
         dpicks, tpicks = peaky_rows(recipe)
         rows = dpicks if shape[0] == int(recipe["draft_vocab"]) else tpicks
@@ -649,6 +666,27 @@ def _load_awq_gptq(cfg: ModelConfig, model_dir: str, scheme: dict, rank: int, tp
         yield name, (w4z_as_symmetric(w) if isinstance(w, W4ZTensor) else w)
 
 
+def _moe_experts(name: str, shape, index: dict, get) -> torch.Tensor:
+    """A layer's fused expert tensor [E, 2I, h] / [E, h, I]: the fused 3-D name as it is (what transformers keeps in memory and
+    save_pretrained writes), or stacked from the published per-expert names mlp.experts.{e}.gate_proj / up_proj / down_proj.weight
+    ([gate ; up] halves per expert)."""
+    if name in index:
+        w = get(name)
+    else:
+        base = name[:name.rindex(".")]              # "...mlp.experts"
+        E = shape[0]
+        miss = [f"{base}.{e}.down_proj.weight" for e in range(E) if f"{base}.{e}.down_proj.weight" not in index]
+        if miss:
+            raise ValueError(f"{name}: the checkpoint has neither the fused tensor nor {miss[0]}")
+        if name.endswith(MOE_GATE_UP):
+            w = torch.stack([torch.cat([get(f"{base}.{e}.gate_proj.weight"), get(f"{base}.{e}.up_proj.weight")], 0) for e in range(E)])
+        else:
+            w = torch.stack([get(f"{base}.{e}.down_proj.weight") for e in range(E)])
+    if not isinstance(w, torch.Tensor) or tuple(w.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected a bf16 tensor of shape {tuple(shape)}, got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
+    return w.contiguous()
+
+
 def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 1,
                      out_device: str | None = None, fp8: bool = False, w4a16: bool = False,
                      mxfp4: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
@@ -764,6 +802,10 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         return t.to(BF16)
 
     for name, shape in param_shapes(cfg):
+        if name.endswith(MOE_GATE_UP) or name.endswith(MOE_DOWN):
+            w = _moe_experts(name, shape, index, get)
+            yield name, (w.to(out_device) if out_device is not None else w)
+            continue
         srcs = _packed_sources(name)
         whole = name in index or name[:-len(".weight")] + ".weight_packed" in index
         parts = [get(s) for s in srcs] if srcs is not None and not whole else [get(name)]
