@@ -11,7 +11,7 @@ from __future__ import annotations
 import os
 from dataclasses import dataclass
 
-from ssd_amd.model_config import ModelConfig, PRESETS
+from ssd_amd.model_config import ModelConfig, PRESETS, presets  # noqa: F401  (PRESETS: re-exported)
 
 
 def resolve_model_config(model: str) -> ModelConfig:
@@ -19,9 +19,9 @@ def resolve_model_config(model: str) -> ModelConfig:
         from transformers import AutoConfig
         return ModelConfig.from_hf(AutoConfig.from_pretrained(model))
     key = model.lower()
-    if key in PRESETS:
-        return PRESETS[key]
-    raise ValueError(f"model must be a directory with config.json or one of {sorted(PRESETS)}; got {model!r}")
+    if key in presets():
+        return presets()[key]
+    raise ValueError(f"model must be a directory with config.json or one of {sorted(presets())}; got {model!r}")
 
 
 @dataclass
@@ -97,10 +97,11 @@ class Config:
     max_lora_rank: int = 64
 
     def _check_moe_target(self) -> None:
-        """A Qwen3-MoE target (hf_config.num_experts > 0) runs bf16 experts on one GPU: everything else is refused by parameter."""
+        """A Qwen3-MoE target (hf_config.num_experts > 0) runs bf16 or MXFP4 experts on one GPU: everything else is refused by
+        parameter."""
         what = f"a mixture-of-experts target ({self.hf_config.num_experts} experts)"
-        if self.quantization is not None:
-            raise ValueError(f"quantization={self.quantization!r} is not supported with {what}: the expert tables are bf16 only")
+        if self.quantization not in (None, "mxfp4"):
+            raise ValueError(f"quantization={self.quantization!r} is not supported with {what}: the expert tables are bf16 or mxfp4 only")
         if self.kv_cache_dtype is not None:
             raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r} is not supported with {what}")
         if self.enable_lora:
@@ -115,6 +116,11 @@ class Config:
             raise ValueError(f"unsupported expert geometry: num_experts={c.num_experts} (8..256, a multiple of 8), "
                              f"num_experts_per_tok={c.num_experts_per_tok} (1..8), moe_intermediate_size={c.moe_intermediate_size} "
                              "(a multiple of 32)")
+        if self.quantization == "mxfp4":        # one device unit of the expert and attention tables covers 128 columns
+            for field, v in (("hidden_size", c.hidden_size), ("num_heads * head_dim", c.num_heads * c.head_dim),
+                             ("moe_intermediate_size", c.moe_intermediate_size)):
+                if v % 128:
+                    raise ValueError(f"quantization='mxfp4' with {what} needs {field} to be a multiple of 128, got {v}")
 
     @property
     def max_blocks(self) -> int:

@@ -10,21 +10,7 @@
 //    operand is the exact weight and the MFMA goes straight into the row accumulator: no offset, no per-group partial, no scale fma.
 #include "common.h"
 #include "gemm_wq.h"
-
-typedef __attribute__((ext_vector_type(2))) __bf16 mx4_bf16x2_t;
-
-// scale byte b (2 <= b <= 252) -> the fp32 2^(b - 127)
-__device__ __forceinline__ float mx4_scale(uint32_t quad, int j) { return __uint_as_float(((quad >> (8 * j)) & 0xffu) << 23); }
-
-// one frag word (8 codes, column e in bits 4e .. 4e+3) -> the 8 bf16 of one MFMA operand slice, each scale * e2m1 (exact)
-__device__ __forceinline__ u32x4_t mx4_to_bf16(uint32_t w, float scale) {
-  u32x4_t r;
-  r[0] = __builtin_bit_cast(uint32_t, (mx4_bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
-  r[1] = __builtin_bit_cast(uint32_t, (mx4_bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
-  r[2] = __builtin_bit_cast(uint32_t, (mx4_bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
-  r[3] = __builtin_bit_cast(uint32_t, (mx4_bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
-  return r;
-}
+#include "mx4.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Layout: row form -> mx4 frag (with an optional destination -> source row map), and back; dequantize into a bf16 frag.

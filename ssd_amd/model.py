@@ -86,11 +86,13 @@ class HipDecoder:
         # cfg.num_experts > 0 (Qwen3-MoE): the MLP of every layer is a router + routed experts (include/ssd_hip_moe.h).  The decoder
         # takes the ROWS route exactly as a quantized target does -- every fused form off -- and launch_gate_up / launch_down, the only
         # two places the MLP lives, run add + norm (rows and frag), router GEMM, route, grouped up GEMM | grouped down GEMM, combine.
-        # bf16 tables, bf16 KV, one rank, no adapters, no taps (Config refuses the rest by name).
+        # bf16 tables, bf16 KV, one rank, no adapters, no taps (Config refuses the rest by name).  quantization="mxfp4": the expert
+        # tables are MXFP4 (codes + scale bytes, include/ssd_hip_moe_mxfp4.h) and q | k | v and o_proj are the quantized linears of a
+        # dense mxfp4 target; the router stays bf16.
         self.moe = cfg.num_experts > 0
         self.moe_trace: list | None = None      # debug hook: a list -> every eager MoE layer appends (router_logits.cpu(), topk_ids.cpu())
-        assert not self.moe or (tp_size == 1 and not force_collectives and taps is None and quantization is None
-                                and kv_cache_dtype is None and max_loras == 0), "MoE targets are single-rank bf16, without taps or adapters"
+        assert not self.moe or (tp_size == 1 and not force_collectives and taps is None and quantization in (None, "mxfp4")
+                                and kv_cache_dtype is None and max_loras == 0), "MoE targets are single-rank bf16 or mxfp4, without taps or adapters"
         # max_loras > 0 (Config.enable_lora): slot tables of LoRA adapters for the four linears of every layer (include/ssd_hip_lora.h,
         # ssd_amd/lora.py), allocated once at the end of __init__ -- before the KV cache is sized, so their memory is counted.  A
         # forward whose batch has an adapted row (lora_active, set by the runner with the row_slot array) takes the ROWS route of
@@ -260,7 +262,8 @@ class HipDecoder:
         # The same scratch serves w4a16 prompts longer than W4_DIRECT_MAX_T rows.
         # ... and mxfp4 prompts longer than MX4_DIRECT_MAX_T rows.
         direct_max = self.W4_DIRECT_MAX_T if self.w4 else self.MX4_DIRECT_MAX_T if self.mx4 else self.FP8_DIRECT_MAX_T
-        self._deq = (z(max(n * k for n, k in pf_shapes[:4])) if self.quantized and max_tokens > direct_max else None)
+        deq_shapes = pf_shapes[:2] if self.moe else pf_shapes[:4]       # a MoE target's experts are never dequantized: q | k | v and o only
+        self._deq = (z(max(n * k for n, k in deq_shapes)) if self.quantized and max_tokens > direct_max else None)
         st = min(T, max_split_tokens)
         self.ws_o = z(st * self.nh * self.max_splits * self.hd, dtype=torch.float32)
         self.ws_ml = z(st * self.nh * self.max_splits * 2, dtype=torch.float32)
@@ -325,6 +328,37 @@ class HipDecoder:
         self.w[name] = out
         return True
 
+    def _load_moe_mx4(self, name: str, w) -> None:
+        """A layer's gate_up / down experts of an mxfp4 target -> "<name>" = E mx4 frag code tables, "<name>_scale" = E scale tables
+        (include/ssd_hip_moe_mxfp4.h).  w: quant.MX4Tensor with a leading expert dimension, taken bit for bit, or a bf16 [E, N, K]
+        tensor, quantized here -- either way one expert at a time, never a whole layer in both forms."""
+        from ssd_amd.weights import MOE_GATE_UP
+        E, up = self.cfg.num_experts, name.endswith(MOE_GATE_UP)
+        N, K = (2 * self.I, self.h) if up else (self.h, self.I)
+        pre = quant.is_prequantized(w)
+        if pre and w.native != "mxfp4":
+            raise ValueError(f"{name}: {w.phrase} tensors cannot load into a mxfp4 decoder")
+        assert tuple(w.shape() if pre else w.shape) == (E, N, K), (name, tuple(w.shape() if pre else w.shape))
+        row_map = quant.gate_up_row_map(N).to(self.device) if up else None
+        qb, sb = N * K // 2, N * K // quant.MX4_BLOCK
+        codes, scales = self._frag(E * qb, torch.uint8), self._frag(E * sb, torch.uint8)
+        for e in range(E):
+            one = quant.to_device(quant.MX4Tensor(w.packed[e], w.scale[e]), self.device) if pre else quant.quantize_mxfp4(w[e].to(self.device))
+            packed, s = one.packed.contiguous(), one.scale.contiguous()
+            assert packed.dtype == torch.uint8 and tuple(packed.shape) == (N, K // 2) and tuple(s.shape) == (N, K // quant.MX4_BLOCK), name
+            quant.check_mxfp4_scales(f"{name}[{e}]", s)
+            MX4.mx4_rows_to_frag(packed, s, codes[e * qb:(e + 1) * qb], scales[e * sb:(e + 1) * sb], N, K, row_map=row_map)
+        self.w[name], self.w[name + "_scale"] = codes, scales
+
+    def _moe_gemm(self, rows_in, name: str, out, T: int, N: int, K: int, epi: int) -> None:
+        """The grouped GEMM over the tables load_weights left under `name`: bf16 fragment-major ones, or MXFP4 codes + scale bytes."""
+        cfg = self.cfg
+        E, k = cfg.num_experts, cfg.num_experts_per_tok
+        if self.mx4:
+            MOE.moe_gemm_mxfp4(rows_in, self.w[name], self.w[name + "_scale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
+        else:
+            MOE.moe_gemm(rows_in, self.w[name], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
+
     def _moe_up(self, li: int, T: int) -> None:
         """The normed rows are in moe_x (rows) and buf_xf (frag): router GEMM -> route -> grouped gate_up GEMM with SiLU * mul."""
         from ssd_amd.weights import MOE_GATE, MOE_GATE_UP
@@ -334,16 +368,14 @@ class HipDecoder:
         MOE.moe_route(self.moe_logits, self.moe_En, T, E, k, cfg.norm_topk_prob, self.moe_ids, self.moe_w, self.moe_offs, self.moe_perm)
         if self.moe_trace is not None:
             self.moe_trace.append((self.moe_logits[:T, :E].cpu(), self.moe_ids[:T * k].view(T, k).cpu()))
-        MOE.moe_gemm(self.moe_x, self.w[p + MOE_GATE_UP], self.moe_offs, self.moe_perm, self.moe_act, T, k, E, 2 * self.I, self.h,
-                     MOE.EPI_UP)
+        self._moe_gemm(self.moe_x, p + MOE_GATE_UP, self.moe_act, T, 2 * self.I, self.h, MOE.EPI_UP)
 
     def _moe_down(self, li: int, T: int) -> None:
         """Grouped down GEMM of moe_act -> moe_d by entry, then the weighted combine into buf_h (rows: the hand-off None)."""
         from ssd_amd.weights import MOE_DOWN
         cfg = self.cfg
         E, k = cfg.num_experts, cfg.num_experts_per_tok
-        MOE.moe_gemm(self.moe_act, self.w[f"model.layers.{li}." + MOE_DOWN], self.moe_offs, self.moe_perm, self.moe_d, T, k, E, self.h,
-                     self.I, MOE.EPI_DOWN)
+        self._moe_gemm(self.moe_act, f"model.layers.{li}." + MOE_DOWN, self.moe_d, T, self.h, self.I, MOE.EPI_DOWN)
         MOE.moe_combine(self.moe_d, self.moe_w, self.buf_h, T, k, self.h)
 
     # ---- LoRA adapters -----------------------------------------------------------------------------
@@ -409,6 +441,8 @@ class HipDecoder:
         _load_w4, _load_mx4), quantizes a bf16 linear as it arrives (never the whole model in both forms) and refuses a linear of
         another kind; everything else -- any host form into a bf16 decoder, embeddings, LM head, norms -- loads as bf16, a host
         form as the exact dequantized matrix."""
+        from ssd_amd.weights import MOE_GATE_UP, MOE_DOWN
+        MOE_EXPERTS = (MOE_GATE_UP, MOE_DOWN)
         kind = self._kind()
         for name, w in weight_iter:
             if type(w) is tuple and len(w) == 2:
@@ -419,6 +453,9 @@ class HipDecoder:
                 elif w.native != kind:
                     raise ValueError(f"{name}: {w.phrase} tensors cannot load into a {kind} decoder")
                 self._load_quantized(name, quant.to_device(w, self.device))
+                continue
+            if self.moe and self.mx4 and name.endswith(MOE_EXPERTS):       # the routed experts: MXFP4 tables, taken or quantized per expert
+                self._load_moe_mx4(name, w)
                 continue
             if quant.is_prequantized(w):        # a bf16 decoder (or a matrix that stays bf16) computes with bf16(s * q)
                 w = quant.to_device(w, self.device).dequantize()

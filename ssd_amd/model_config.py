@@ -119,3 +119,16 @@ PRESETS = {
     "eagle3-llama-3.3-70b": ModelConfig("eagle3", 6144, 1, 48, 8, 128, 16384, 128256, 1e-5, 5e5, 131072, False,
                                         draft_vocab_size=32000, d_model_target=8192),
 }
+
+# Mixture-of-experts targets that load on one GPU only with quantization="mxfp4" (public config.json shapes; the remaining fields are
+# the family's 30B entry's).  Kept beside PRESETS, which Config.resolve_model_config consults first: tests/test_moe_cpu.py pins
+# PRESETS to exactly one MoE entry.  Qwen3-235B-A22B: ~470 GB in bf16, ~121 GB of MXFP4 experts.
+MOE_PRESETS = {
+    "qwen3-235b-a22b": ModelConfig("qwen3_moe", 4096, 94, 64, 4, 128, 12288, 151936, 1e-6, 1e6, 40960, False, True,
+                                   num_experts=128, num_experts_per_tok=8, moe_intermediate_size=1536, norm_topk_prob=True),
+}
+
+
+def presets() -> dict:
+    """The one registry of preset names: PRESETS and MOE_PRESETS together (iterate or look up here, not in either dictionary)."""
+    return {**PRESETS, **MOE_PRESETS}

@@ -310,13 +310,15 @@ E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -
 
 
 class MX4Tensor(NamedTuple):
-    """An MXFP4 decoder linear in the host form: packed uint8 [N, K / 2], scale uint8 [N, K / 32]."""
+    """An MXFP4 decoder linear in the host form: packed uint8 [N, K / 2], scale uint8 [N, K / 32].  A layer's routed experts travel as
+    ONE MX4Tensor whose fields carry a leading expert dimension: packed [E, N, K / 2], scale [E, N, K / 32] (weights._moe_experts makes
+    it, HipDecoder._load_moe_mx4 consumes it one expert at a time); shape() and dequantize() then answer [E, N, K]."""
     packed: torch.Tensor
     scale: torch.Tensor
     native, phrase = "mxfp4", "MXFP4"
 
-    def shape(self) -> tuple[int, int]:
-        return self.packed.shape[0], self.packed.shape[1] * 2
+    def shape(self) -> tuple:
+        return (*self.packed.shape[:-1], self.packed.shape[-1] * 2)
 
     def dequantize(self) -> torch.Tensor:
         return dequantize_mxfp4(*self)
@@ -342,7 +344,7 @@ def pack_mxfp4(codes: torch.Tensor) -> torch.Tensor:
 def unpack_mxfp4(packed: torch.Tensor) -> torch.Tensor:
     """uint8 [N, K / 2] -> e2m1 codes uint8 [N, K] in 0..15."""
     p = packed.to(torch.int32)
-    return torch.stack((p & 0xF, p >> 4), dim=-1).reshape(packed.shape[0], -1).to(torch.uint8)
+    return torch.stack((p & 0xF, p >> 4), dim=-1).reshape(*packed.shape[:-1], -1).to(torch.uint8)
 
 
 def quantize_mxfp4(w: torch.Tensor) -> MX4Tensor:
@@ -374,7 +376,7 @@ def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     given MXFP4 tensors)."""
     lut = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=packed.device)
     v = lut[unpack_mxfp4(packed).long()]
-    s = (scale.to(torch.int32) << 23).view(torch.float32).repeat_interleave(MX4_BLOCK, dim=1)
+    s = (scale.to(torch.int32) << 23).view(torch.float32).repeat_interleave(MX4_BLOCK, dim=-1)
     return (v * s).to(torch.bfloat16)
 
 

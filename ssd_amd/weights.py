@@ -666,22 +666,38 @@ def _load_awq_gptq(cfg: ModelConfig, model_dir: str, scheme: dict, rank: int, tp
         yield name, (w4z_as_symmetric(w) if isinstance(w, W4ZTensor) else w)
 
 
-def _moe_experts(name: str, shape, index: dict, get) -> torch.Tensor:
+def _moe_experts(name: str, shape, index: dict, get, target: str | None = None):
     """A layer's fused expert tensor [E, 2I, h] / [E, h, I]: the fused 3-D name as it is (what transformers keeps in memory and
     save_pretrained writes), or stacked from the published per-expert names mlp.experts.{e}.gate_proj / up_proj / down_proj.weight
-    ([gate ; up] halves per expert)."""
+    ([gate ; up] halves per expert).  Per-expert tensors of an MXFP4 checkpoint (.weight_packed + .weight_scale) are stacked bit for
+    bit into ONE quant.MX4Tensor with a leading expert dimension (packed [E, N, K / 2], scale [E, N, K / 32]): an mxfp4 target gets that
+    host form, any other consumer its exact dequantized bf16 image."""
+    from ssd_amd import quant
     if name in index:
         w = get(name)
     else:
         base = name[:name.rindex(".")]              # "...mlp.experts"
         E = shape[0]
-        miss = [f"{base}.{e}.down_proj.weight" for e in range(E) if f"{base}.{e}.down_proj.weight" not in index]
+        stored = lambda n: n in index or n[:-len(".weight")] + MXFP4_PACKED_SUFFIX in index
+        miss = [f"{base}.{e}.down_proj.weight" for e in range(E) if not stored(f"{base}.{e}.down_proj.weight")]
         if miss:
             raise ValueError(f"{name}: the checkpoint has neither the fused tensor nor {miss[0]}")
-        if name.endswith(MOE_GATE_UP):
-            w = torch.stack([torch.cat([get(f"{base}.{e}.gate_proj.weight"), get(f"{base}.{e}.up_proj.weight")], 0) for e in range(E)])
+        srcs = ("gate_proj", "up_proj") if name.endswith(MOE_GATE_UP) else ("down_proj",)
+        parts = [[get(f"{base}.{e}.{s}.weight") for s in srcs] for e in range(E)]
+        if all(isinstance(p, quant.MX4Tensor) for row in parts for p in row):
+            rows = [quant.cat_rows(row) for row in parts]
+            w = quant.MX4Tensor(torch.stack([r.packed for r in rows]), torch.stack([r.scale for r in rows]))
+            if w.shape() != tuple(shape):
+                raise ValueError(f"{name}: expected MXFP4 experts of shape {tuple(shape)}, got {w.shape()}")
+            if target == "mxfp4":
+                return w
+            w = w.dequantize()
         else:
-            w = torch.stack([get(f"{base}.{e}.down_proj.weight") for e in range(E)])
+            for row in parts:
+                for p in row:
+                    if quant.is_prequantized(p):        # fp8 / int4 experts, or an expert only partly MXFP4: not a form any target runs
+                        raise ValueError(f"{name}: per-expert {p.phrase} tensors are not supported (experts load as bf16, or all as MXFP4)")
+            w = torch.stack([torch.cat(row, 0) for row in parts])
     if not isinstance(w, torch.Tensor) or tuple(w.shape) != tuple(shape):
         raise ValueError(f"{name}: expected a bf16 tensor of shape {tuple(shape)}, got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
     return w.contiguous()
@@ -700,8 +716,10 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         weight_scale_inv expanded to one row of block scales per output row, then concatenated;
       * pack-quantized int4: quant.W4Tensor(packed int32 [N, K/8], scale bf16 [N, K/128]); fp16 / fp32 scales are rounded to bf16 once;
       * AutoAWQ / GPTQ int4 (_load_awq_gptq): quant.W4ZTensor(packed, scale, zero), a plain W4Tensor when all its zero points are 8;
-      * MXFP4: quant.MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32]); scale bytes outside 2..252 are refused.
+      * MXFP4: quant.MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32]); scale bytes outside 2..252 are refused.  A MoE layer's
+        per-expert tensors become one MX4Tensor with a leading expert dimension (_moe_experts).
     Unquantized tensors (e.g. the LM head) load as bf16."""
+    from ssd_amd import quant
     from ssd_amd.quant import FP8, FP8Tensor, W4Tensor, MX4Tensor, check_mxfp4_scales, FP8_BLOCK, FP8BTensor, expand_fp8_block_scales
     assert fp8 + w4a16 + mxfp4 <= 1
     target = "fp8" if fp8 else "w4a16" if w4a16 else "mxfp4" if mxfp4 else None
@@ -803,8 +821,8 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
 
     for name, shape in param_shapes(cfg):
         if name.endswith(MOE_GATE_UP) or name.endswith(MOE_DOWN):
-            w = _moe_experts(name, shape, index, get)
-            yield name, (w.to(out_device) if out_device is not None else w)
+            w = _moe_experts(name, shape, index, get, target)
+            yield name, (quant.to_device(w, out_device) if quant.is_prequantized(w) else w.to(out_device) if out_device is not None else w)
             continue
         srcs = _packed_sources(name)
         whole = name in index or name[:-len(".weight")] + ".weight_packed" in index
