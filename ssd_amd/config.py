@@ -97,11 +97,11 @@ class Config:
     max_lora_rank: int = 64
 
     def _check_moe_target(self) -> None:
-        """A Qwen3-MoE target (hf_config.num_experts > 0) runs bf16 or MXFP4 experts on one GPU: everything else is refused by
-        parameter."""
+        """A Qwen3-MoE target (hf_config.num_experts > 0) runs bf16, MXFP4 or block-scaled FP8 experts on one GPU: everything else is
+        refused by parameter."""
         what = f"a mixture-of-experts target ({self.hf_config.num_experts} experts)"
-        if self.quantization not in (None, "mxfp4"):
-            raise ValueError(f"quantization={self.quantization!r} is not supported with {what}: the expert tables are bf16 or mxfp4 only")
+        if self.quantization not in (None, "mxfp4", "fp8"):
+            raise ValueError(f"quantization={self.quantization!r} is not supported with {what}: the expert tables are bf16, mxfp4 or fp8 only")
         if self.kv_cache_dtype is not None:
             raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r} is not supported with {what}")
         if self.enable_lora:
@@ -116,11 +116,11 @@ class Config:
             raise ValueError(f"unsupported expert geometry: num_experts={c.num_experts} (8..256, a multiple of 8), "
                              f"num_experts_per_tok={c.num_experts_per_tok} (1..8), moe_intermediate_size={c.moe_intermediate_size} "
                              "(a multiple of 32)")
-        if self.quantization == "mxfp4":        # one device unit of the expert and attention tables covers 128 columns
+        if self.quantization in ("mxfp4", "fp8"):       # one device unit (mxfp4) / one scale block (fp8) of the expert tables covers 128 columns
             for field, v in (("hidden_size", c.hidden_size), ("num_heads * head_dim", c.num_heads * c.head_dim),
                              ("moe_intermediate_size", c.moe_intermediate_size)):
                 if v % 128:
-                    raise ValueError(f"quantization='mxfp4' with {what} needs {field} to be a multiple of 128, got {v}")
+                    raise ValueError(f"quantization={self.quantization!r} with {what} needs {field} to be a multiple of 128, got {v}")
 
     @property
     def max_blocks(self) -> int:

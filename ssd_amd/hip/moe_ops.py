@@ -1,9 +1,11 @@
-"""ctypes table and torch front end of the mixture-of-experts entry points (include/ssd_hip_moe.h, include/ssd_hip_moe_mxfp4.h).
+"""ctypes table and torch front end of the mixture-of-experts entry points (include/ssd_hip_moe.h, include/ssd_hip_moe_mxfp4.h,
+include/ssd_hip_moe_fp8b.h).
 
 Kept apart from ``lib.SIGNATURES`` and the other additive tables: these bind on the same libssdhip.so.  As in ops.py, nothing here
 computes in torch; the calls enqueue on the current stream and are hipGraph-capturable.  The expert tables are laid out by
 ``ops.rows_to_frag`` (mode 1 for gate_up, mode 0 for down), one expert after the other; MXFP4 expert tables by
-``mx4_ops.mx4_rows_to_frag`` per expert (gate_up with ``quant.gate_up_row_map``), codes and scale bytes in one table each.
+``mx4_ops.mx4_rows_to_frag`` per expert (gate_up with ``quant.gate_up_row_map``), codes and scale bytes in one table each; block-scaled FP8
+expert tables by ``quant_ops.fp8_rows_to_frag`` + ``quant.fp8_block_group_scales`` per expert, codes and fp32 group scales in one table each.
 """
 from __future__ import annotations
 
@@ -29,6 +31,11 @@ MOE_MX4_SIGNATURES = {
     "ssd_moe_gemm_mxfp4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
 }
 
+# name -> argtypes, exactly include/ssd_hip_moe_fp8b.h
+MOE_FP8B_SIGNATURES = {
+    "ssd_moe_gemm_fp8b": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+}
+
 
 def load_moe_library():
     return bind(MOE_SIGNATURES)
@@ -36,6 +43,10 @@ def load_moe_library():
 
 def load_moe_mx4_library():
     return bind(MOE_MX4_SIGNATURES)
+
+
+def load_moe_fp8b_library():
+    return bind(MOE_FP8B_SIGNATURES)
 
 
 def moe_route(logits, ld: int, T: int, E: int, k: int, norm: bool, topk_ids, topk_w, offs, perm):
@@ -55,6 +66,12 @@ def moe_gemm_mxfp4(rows_in, q_frag, s_frag, offs, perm, out, T: int, k: int, E: 
     """moe_gemm over E MXFP4 tables [N][K]: q_frag E * N * K / 2 bytes of mx4 frag codes, s_frag E * N * K / 32 scale bytes."""
     _check(load_moe_mx4_library().ssd_moe_gemm_mxfp4(_p(rows_in), _p(q_frag), _p(s_frag), _p(offs), _p(perm), _p(out), T, k, E, N, K,
                                                      epilogue, _stream()), "ssd_moe_gemm_mxfp4")
+
+
+def moe_gemm_fp8b(rows_in, q_frag, s_grp, offs, perm, out, T: int, k: int, E: int, N: int, K: int, epilogue: int):
+    """moe_gemm over E block-scaled FP8 tables [N][K]: q_frag E * N * K bytes of fp8 frag codes, s_grp fp32 [E][N / 16][K / 128]."""
+    _check(load_moe_fp8b_library().ssd_moe_gemm_fp8b(_p(rows_in), _p(q_frag), _p(s_grp), _p(offs), _p(perm), _p(out), T, k, E, N, K,
+                                                     epilogue, _stream()), "ssd_moe_gemm_fp8b")
 
 
 def moe_combine(d_rows, topk_w, h_rows, T: int, k: int, H: int):

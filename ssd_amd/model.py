@@ -88,11 +88,13 @@ class HipDecoder:
         # two places the MLP lives, run add + norm (rows and frag), router GEMM, route, grouped up GEMM | grouped down GEMM, combine.
         # bf16 tables, bf16 KV, one rank, no adapters, no taps (Config refuses the rest by name).  quantization="mxfp4": the expert
         # tables are MXFP4 (codes + scale bytes, include/ssd_hip_moe_mxfp4.h) and q | k | v and o_proj are the quantized linears of a
-        # dense mxfp4 target; the router stays bf16.
+        # dense mxfp4 target; the router stays bf16.  quantization="fp8": the expert tables are block-scaled FP8 (e4m3 codes + one fp32
+        # scale per 16-row group and 128-column block, include/ssd_hip_moe_fp8b.h), q | k | v and o_proj the quantized linears of a
+        # dense fp8 target, per-row or block-scaled as they arrive; the experts are never dequantized.
         self.moe = cfg.num_experts > 0
         self.moe_trace: list | None = None      # debug hook: a list -> every eager MoE layer appends (router_logits.cpu(), topk_ids.cpu())
-        assert not self.moe or (tp_size == 1 and not force_collectives and taps is None and quantization in (None, "mxfp4")
-                                and kv_cache_dtype is None and max_loras == 0), "MoE targets are single-rank bf16 or mxfp4, without taps or adapters"
+        assert not self.moe or (tp_size == 1 and not force_collectives and taps is None and quantization in (None, "mxfp4", "fp8")
+                                and kv_cache_dtype is None and max_loras == 0), "MoE targets are single-rank bf16, mxfp4 or fp8, without taps or adapters"
         # max_loras > 0 (Config.enable_lora): slot tables of LoRA adapters for the four linears of every layer (include/ssd_hip_lora.h,
         # ssd_amd/lora.py), allocated once at the end of __init__ -- before the KV cache is sized, so their memory is counted.  A
         # forward whose batch has an adapted row (lora_active, set by the runner with the row_slot array) takes the ROWS route of
@@ -150,6 +152,9 @@ class HipDecoder:
         if self.mx4 and any(k % quant.MX4_GROUP for k in (self.h, self.qn, self.I)):
             raise ValueError(f"quantization='mxfp4' needs hidden_size, num_heads * head_dim and intermediate_size to be multiples of "
                              f"{quant.MX4_GROUP} (four 32-column blocks: one device unit), got {self.h}, {self.qn}, {self.I}")
+        if self.fp8 and self.moe and any(k % quant.FP8_BLOCK for k in (self.h, self.qn, self.I)):
+            raise ValueError(f"quantization='fp8' with a mixture-of-experts target needs hidden_size, num_heads * head_dim and "
+                             f"moe_intermediate_size to be multiples of {quant.FP8_BLOCK} (one scale block), got {self.h}, {self.qn}, {self.I}")
         self.block_size, self.max_blocks = block_size, max_blocks
         self.max_tokens = max_tokens
         self.max_logit_rows = max_logit_rows or max_tokens
@@ -350,12 +355,37 @@ class HipDecoder:
             MX4.mx4_rows_to_frag(packed, s, codes[e * qb:(e + 1) * qb], scales[e * sb:(e + 1) * sb], N, K, row_map=row_map)
         self.w[name], self.w[name + "_scale"] = codes, scales
 
+    def _load_moe_fp8b(self, name: str, w) -> None:
+        """A layer's gate_up / down experts of an fp8 target -> "<name>" = E fp8 frag code tables, "<name>_bscale" = E group scale tables
+        fp32 [N / 16, K / 128] (include/ssd_hip_moe_fp8b.h).  w: quant.FP8BTensor with a leading expert dimension, taken bit for bit, or
+        a bf16 [E, N, K] tensor, quantized here with quant.quantize_fp8_block -- either way one expert at a time."""
+        from ssd_amd.weights import MOE_GATE_UP
+        E, up = self.cfg.num_experts, name.endswith(MOE_GATE_UP)
+        N, K = (2 * self.I, self.h) if up else (self.h, self.I)
+        pre = quant.is_prequantized(w)
+        if pre and not isinstance(w, quant.FP8BTensor):
+            raise ValueError(f"{name}: {w.phrase} expert tensors cannot load into a fp8 decoder (block-scaled fp8 or bf16 only)")
+        assert tuple(w.shape() if pre else w.shape) == (E, N, K), (name, tuple(w.shape() if pre else w.shape))
+        row_map = quant.gate_up_row_map(N).to(self.device) if up else None
+        KB = K // quant.FP8_BLOCK
+        codes, scales = self._frag(E * N * K, torch.uint8), self._frag(E * (N // 16) * KB, torch.float32)
+        for e in range(E):
+            one = quant.to_device(quant.FP8BTensor(w.codes[e], w.rowscale[e]), self.device) if pre else quant.quantize_fp8_block(w[e].to(self.device))
+            q, s = one.codes.contiguous(), one.rowscale.to(torch.float32).contiguous()
+            assert q.dtype == quant.FP8 and tuple(q.shape) == (N, K) and tuple(s.shape) == (N, KB), (name, q.dtype, q.shape, s.shape)
+            Q.fp8_rows_to_frag(q.view(torch.uint8), codes[e * N * K:(e + 1) * N * K], N, K, row_map=row_map)
+            scales.view(E, N // 16, KB)[e].copy_(quant.fp8_block_group_scales(s, row_map, f"{name}[{e}]"))
+        self.w[name], self.w[name + "_bscale"] = codes, scales
+
     def _moe_gemm(self, rows_in, name: str, out, T: int, N: int, K: int, epi: int) -> None:
-        """The grouped GEMM over the tables load_weights left under `name`: bf16 fragment-major ones, or MXFP4 codes + scale bytes."""
+        """The grouped GEMM over the tables load_weights left under `name`: bf16 fragment-major ones, MXFP4 codes + scale bytes, or
+        block-scaled FP8 codes + group scales."""
         cfg = self.cfg
         E, k = cfg.num_experts, cfg.num_experts_per_tok
         if self.mx4:
             MOE.moe_gemm_mxfp4(rows_in, self.w[name], self.w[name + "_scale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
+        elif self.fp8:
+            MOE.moe_gemm_fp8b(rows_in, self.w[name], self.w[name + "_bscale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
         else:
             MOE.moe_gemm(rows_in, self.w[name], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
 
@@ -456,6 +486,9 @@ class HipDecoder:
                 continue
             if self.moe and self.mx4 and name.endswith(MOE_EXPERTS):       # the routed experts: MXFP4 tables, taken or quantized per expert
                 self._load_moe_mx4(name, w)
+                continue
+            if self.moe and self.fp8 and name.endswith(MOE_EXPERTS):       # ... or block-scaled FP8 tables, likewise
+                self._load_moe_fp8b(name, w)
                 continue
             if quant.is_prequantized(w):        # a bf16 decoder (or a matrix that stays bf16) computes with bf16(s * q)
                 w = quant.to_device(w, self.device).dequantize()

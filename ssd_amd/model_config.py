@@ -120,9 +120,9 @@ PRESETS = {
                                         draft_vocab_size=32000, d_model_target=8192),
 }
 
-# Mixture-of-experts targets that load on one GPU only with quantization="mxfp4" (public config.json shapes; the remaining fields are
+# Mixture-of-experts targets that load on one GPU only with quantization="mxfp4" or, by calculation, "fp8" (public config.json shapes; the remaining fields are
 # the family's 30B entry's).  Kept beside PRESETS, which Config.resolve_model_config consults first: tests/test_moe_cpu.py pins
-# PRESETS to exactly one MoE entry.  Qwen3-235B-A22B: ~470 GB in bf16, ~121 GB of MXFP4 experts.
+# PRESETS to exactly one MoE entry.  Qwen3-235B-A22B: ~470 GB in bf16, ~121 GB of MXFP4 experts, ~227 GB of FP8 ones.
 MOE_PRESETS = {
     "qwen3-235b-a22b": ModelConfig("qwen3_moe", 4096, 94, 64, 4, 128, 12288, 151936, 1e-6, 1e6, 40960, False, True,
                                    num_experts=128, num_experts_per_tok=8, moe_intermediate_size=1536, norm_topk_prob=True),

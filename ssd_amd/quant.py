@@ -98,12 +98,14 @@ FP8_BLOCK = 128
 
 class FP8BTensor(NamedTuple):
     """A block-scaled FP8 decoder linear on the host: codes float8_e4m3fn [N, K], rowscale fp32 [N, ceil(K / 128)] (row n holds
-    the scales of the block row its source tensor put row n in)."""
+    the scales of the block row its source tensor put row n in).  A layer's routed experts travel as ONE FP8BTensor whose fields carry a
+    leading expert dimension: codes [E, N, K], rowscale [E, N, K / 128] (weights._moe_experts makes it, HipDecoder._load_moe_fp8b
+    consumes it one expert at a time); shape() and dequantize() then answer [E, N, K]."""
     codes: torch.Tensor
     rowscale: torch.Tensor
     native, phrase = "fp8", "block-scaled fp8"
 
-    def shape(self) -> tuple[int, int]:
+    def shape(self) -> tuple:
         return tuple(self.codes.shape)
 
     def dequantize(self) -> torch.Tensor:
@@ -117,7 +119,7 @@ def expand_fp8_block_scales(s: torch.Tensor, N: int) -> torch.Tensor:
 
 
 def _fp8_block_elem_scales(rowscale: torch.Tensor, K: int) -> torch.Tensor:
-    return rowscale.float().repeat_interleave(FP8_BLOCK, dim=1)[:, :K]
+    return rowscale.float().repeat_interleave(FP8_BLOCK, dim=-1)[..., :K]
 
 
 def quantize_fp8_block(w: torch.Tensor) -> FP8BTensor:
@@ -136,7 +138,7 @@ def quantize_fp8_block(w: torch.Tensor) -> FP8BTensor:
 
 def dequantize_fp8_block(codes: torch.Tensor, rowscale: torch.Tensor) -> torch.Tensor:
     """bf16(s * q), the product in fp32: the weights a block-scaled fp8 target computes with, as a bf16 matrix."""
-    return (codes.float() * _fp8_block_elem_scales(rowscale, codes.shape[1])).to(torch.bfloat16)
+    return (codes.float() * _fp8_block_elem_scales(rowscale, codes.shape[-1])).to(torch.bfloat16)
 
 
 def fp8_block_group_scales(rowscale: torch.Tensor, row_map: torch.Tensor | None, name: str = "") -> torch.Tensor:

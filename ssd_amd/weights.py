@@ -671,7 +671,9 @@ def _moe_experts(name: str, shape, index: dict, get, target: str | None = None):
     save_pretrained writes), or stacked from the published per-expert names mlp.experts.{e}.gate_proj / up_proj / down_proj.weight
     ([gate ; up] halves per expert).  Per-expert tensors of an MXFP4 checkpoint (.weight_packed + .weight_scale) are stacked bit for
     bit into ONE quant.MX4Tensor with a leading expert dimension (packed [E, N, K / 2], scale [E, N, K / 32]): an mxfp4 target gets that
-    host form, any other consumer its exact dequantized bf16 image."""
+    host form, any other consumer its exact dequantized bf16 image.  Per-expert tensors of a block-scaled fp8 checkpoint (.weight
+    float8_e4m3fn + .weight_scale_inv) likewise become ONE quant.FP8BTensor (codes [E, N, K], rowscale [E, N, K / 128]) for an fp8
+    target, the exact bf16(s * q) image for any other consumer."""
     from ssd_amd import quant
     if name in index:
         w = get(name)
@@ -692,11 +694,21 @@ def _moe_experts(name: str, shape, index: dict, get, target: str | None = None):
             if target == "mxfp4":
                 return w
             w = w.dequantize()
+        elif all(isinstance(p, quant.FP8BTensor) for row in parts for p in row):
+            # block-scaled fp8 experts: every source tensor's scales are already one row per output row (get -> get_fp8_block)
+            rows = [quant.cat_rows(row) for row in parts]
+            w = quant.FP8BTensor(torch.stack([r.codes for r in rows]), torch.stack([r.rowscale for r in rows]))
+            if w.shape() != tuple(shape):
+                raise ValueError(f"{name}: expected block-scaled fp8 experts of shape {tuple(shape)}, got {w.shape()}")
+            if target == "fp8":
+                return w
+            w = w.dequantize()
         else:
             for row in parts:
                 for p in row:
-                    if quant.is_prequantized(p):        # fp8 / int4 experts, or an expert only partly MXFP4: not a form any target runs
-                        raise ValueError(f"{name}: per-expert {p.phrase} tensors are not supported (experts load as bf16, or all as MXFP4)")
+                    if quant.is_prequantized(p):        # per-row fp8 / int4 experts, or experts only partly quantized: not a form any target runs
+                        raise ValueError(f"{name}: per-expert {p.phrase} tensors are not supported (experts load as bf16, or all as MXFP4, "
+                                         "or all as block-scaled fp8)")
             w = torch.stack([torch.cat(row, 0) for row in parts])
     if not isinstance(w, torch.Tensor) or tuple(w.shape) != tuple(shape):
         raise ValueError(f"{name}: expected a bf16 tensor of shape {tuple(shape)}, got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
@@ -717,7 +729,8 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
       * pack-quantized int4: quant.W4Tensor(packed int32 [N, K/8], scale bf16 [N, K/128]); fp16 / fp32 scales are rounded to bf16 once;
       * AutoAWQ / GPTQ int4 (_load_awq_gptq): quant.W4ZTensor(packed, scale, zero), a plain W4Tensor when all its zero points are 8;
       * MXFP4: quant.MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32]); scale bytes outside 2..252 are refused.  A MoE layer's
-        per-expert tensors become one MX4Tensor with a leading expert dimension (_moe_experts).
+        per-expert tensors become one MX4Tensor with a leading expert dimension (_moe_experts), and those of a block-scaled fp8
+        checkpoint one FP8BTensor with a leading expert dimension.
     Unquantized tensors (e.g. the LM head) load as bf16."""
     from ssd_amd import quant
     from ssd_amd.quant import FP8, FP8Tensor, W4Tensor, MX4Tensor, check_mxfp4_scales, FP8_BLOCK, FP8BTensor, expand_fp8_block_scales
