@@ -122,6 +122,27 @@ class Config:
                 if v % 128:
                     raise ValueError(f"quantization={self.quantization!r} with {what} needs {field} to be a multiple of 128, got {v}")
 
+    def _check_windows(self) -> None:
+        """Sliding-window models (ModelConfig.sliding_window / layer_windows; include/ssd_hip_swa.h) run as the target in every mode
+        and as the synchronous draft, on one GPU: everything else is refused by parameter."""
+        t, d = self.hf_config, self.draft_hf_config if self.speculate else None
+        for c in (t, d):
+            if c is not None:
+                c.check_windows()
+        if d is not None and d.windowed and self.draft_async:
+            raise ValueError(f"draft={self.draft!r} has sliding-window layers: draft_async=True is not supported with a windowed draft "
+                             "(the draft-tree mask is not windowed)")
+        if not (t.windowed or (d is not None and d.windowed)):
+            return
+        what = "a sliding-window model"
+        if self.use_eagle:
+            raise ValueError(f"use_eagle=True is not supported with {what}")
+        if self.num_gpus > 1 and not (self.speculate and self.draft_async and self.num_gpus - self.num_draft_gpus == 1):
+            raise ValueError(f"num_gpus={self.num_gpus} is not supported with {what}: windowed attention runs on one GPU (an "
+                             "asynchronous draft may have its own)")
+        if t.windowed and t.num_experts > 0:
+            raise ValueError(f"sliding_window={t.sliding_window} is not supported with a mixture-of-experts target ({t.num_experts} experts)")
+
     @property
     def max_blocks(self) -> int:
         return -(-self.max_model_len // self.kvcache_block_size)
@@ -203,6 +224,7 @@ class Config:
                 assert 0 <= min(self.fan_out_list + self.fan_out_list_miss) and max(self.fan_out_list + self.fan_out_list_miss) <= 15, \
                     "fan-out per position must be in 0..15"
                 assert sum(self.fan_out_list_miss) == sum(self.fan_out_list), "hit and miss fan-out lists must have the same sum"
+        self._check_windows()
         if self.sampler_x is not None:
             assert self.speculate and self.draft_async, "sampler_x requires draft_async (reference model_runner.py:262-263)"
             assert self.sampler_x > 0 and self.async_fan_out + 1 <= 8

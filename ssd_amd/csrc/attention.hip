@@ -44,6 +44,8 @@ struct AttnParams {
   // FP8 KV cache (attn_kernel<.., KV8 = true>, ssd_attn_paged_fp8 below): kc / vc are e4m3 codes, one fp32 scale per kv head
   const float* k_scale;      // [nkv] or null -> 1.0
   const float* v_scale;
+  // sliding window (attn_kernel<.., WIN = true>, ssd_attn_paged_window below; include/ssd_hip_swa.h): mode 0 only, 0 = none
+  int window;
 };
 
 // LDS per wave: the V tile (32 keys x HD bf16) during the scan, then the wave's partial (O fp32 [RT*16][HD],
@@ -63,9 +65,17 @@ constexpr int attn_region_bytes() { return RT * 16 * HD * 4 + RT * 16 * 8; }
 // in 16-byte chunks of 16 codes and widened while it is staged into LDS as the same bf16 tile, so the transpose read, the softmax,
 // P.V, the merge and the combine are the bf16 kernel's.  k_scale[h] folds into the logit scale, v_scale[h] into the output / the
 // split partials (h is fixed per workgroup).  Rows past ctx are clamped exactly as for bf16: never addressed.
-template <int HD, int RT, int KT, bool OPROJ = false, bool KV8 = false>
+// WIN (include/ssd_hip_swa.h; mode 0): a row with causal limit lim sees the keys [max(0, lim - window), lim).  The workgroup's scan
+// starts at kmin = its first row's left edge rounded down to a key tile instead of at key 0 -- the (split, wave) shares deal the
+// tiles of [kmin, kmax), so the tiles in front of the window are neither loaded nor counted, and with kmin = 0 (no row cut off) the
+// dealing, and with it every bit of the result, is the unwindowed kernel's.  Only the tiles below kmax - window can hide a key of
+// some row on the left: they alone re-mask their scores (a wave-uniform branch; the interior tiles run the unwindowed tile).  A
+// share that gets no tile leaves m = -inf, l = 0, O = 0, which both merges weigh with exp2(-inf - Ms) = 0 (Ms is 0 when every
+// share is empty).  Rows in front of the workgroup's left edge are never addressed: see the clamp at issue_k.
+template <int HD, int RT, int KT, bool OPROJ = false, bool KV8 = false, bool WIN = false>
 __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
   static_assert(!(OPROJ && KV8), "no fused o_proj form over an fp8 cache");
+  static_assert(!(OPROJ && WIN), "no fused o_proj form under a sliding window");
   constexpr int ES = KV8 ? 1 : 2;           // bytes per cache element
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KTS = OPROJ ? 7 : 6;        // trace slot (profiling builds only)
@@ -131,6 +141,11 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
   }
   const int stride = p.splits * W * 32;
   int k0 = (z * W + wave) * 32;
+  int wlo = 0;      // WIN: the lowest key any row of this workgroup sees = its first row's left edge (later rows start later)
+  if constexpr (WIN) {
+    wlo = max(0, ctx - (Tq - 1 - (tile_base * 16) / G) - p.window);
+    k0 += wlo & ~31;
+  }
 
   float m[RT], lsum[RT];
   f32x4_t o[RT][DT];
@@ -157,12 +172,38 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
   auto half_base = [&](const bf16_t* base, int page, int key0) -> const char* {
     return reinterpret_cast<const char*>(base) + (((size_t)page * p.nkv + h) * p.bs + (key0 & (p.bs - 1))) * (HD * ES);
   };
+  // WIN: the mirror image on the left.  Rows in front of wlo (they exist in the workgroup's first tile only) are clamped to
+  // the tile's first visible row, and a first half that lies wholly in front of wlo is redirected to the second half's page:
+  // no K / V row below wlo is addressed and no page wholly below it is named, so such pages may hold anything (p = 0 meets a
+  // finite V in the P.V MFMA).  wlo <= ctx - 1, so the two clamps leave at least one row; both can act on one tile.
+  // edges(): per half, the base it reads from and the [lo, hi] its row index is clamped to.
+  struct HalfEdge { const char* b; int lo, hi; };
+  auto edges = [&](const bf16_t* base, int kt, int pa, int pb, HalfEdge& e0, HalfEdge& e1) {
+    const int cl = ctx - 1 - kt, fl = max(wlo - kt, 0);    // last / first addressable row of the tile; fl <= cl, fl < 32
+    const bool avalid = fl < 16, bvalid = cl >= 16;        // at least one holds
+    const char* a = half_base(base, pa, kt);
+    const char* b = half_base(base, pb, kt + 16);
+    e0 = avalid ? HalfEdge{a, fl, cl} : HalfEdge{b, fl - 16, cl - 16};
+    e1 = bvalid ? HalfEdge{b, fl - 16, cl - 16} : HalfEdge{a, fl, cl};
+  };
   // K operand of one (16-key half, k-step) as loaded: 8 bf16, or 8 codes that kwide() widens in front of the MFMA
   using kraw_t = typename std::conditional<KV8, u32x2_t, u32x4_t>::type;
   auto kwide = [](const kraw_t& k) -> u32x4_t {
     if constexpr (KV8) return kv8_to_bf16x8(k[0], k[1]); else return k;
   };
   auto issue_k = [&](int kt, int pa, int pb, kraw_t (&kf)[2][DS]) {
+    if constexpr (WIN) {
+      HalfEdge e0, e1;
+      edges(p.kc, kt, pa, pb, e0, e1);
+      const uint32_t o0 = (uint32_t)(max(min(r16, e0.hi), e0.lo) * HD + g4 * 8) * (uint32_t)ES;
+      const uint32_t o1 = (uint32_t)(max(min(r16, e1.hi), e1.lo) * HD + g4 * 8) * (uint32_t)ES;
+#pragma unroll
+      for (int ds = 0; ds < DS; ++ds) {
+        kf[0][ds] = *reinterpret_cast<const kraw_t*>(e0.b + o0 + ds * 32 * ES);
+        kf[1][ds] = *reinterpret_cast<const kraw_t*>(e1.b + o1 + ds * 32 * ES);
+      }
+      return;
+    }
     const int cl = ctx - 1 - kt;                  // >= 0 for every tile we touch
     const bool bvalid = cl >= 16;
     const char* b0 = half_base(p.kc, pa, kt);
@@ -176,6 +217,20 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
     }
   };
   auto issue_v = [&](int kt, int pa, int pb, u32x4_t (&vf)[NV]) {
+    if constexpr (WIN) {
+      HalfEdge e0, e1;
+      edges(p.vc, kt, pa, pb, e0, e1);
+#pragma unroll
+      for (int it = 0; it < NV; ++it) {
+        constexpr int KPI = 64 / CH;
+        const int key = it * KPI + lane / CH;
+        const bool second = (it * KPI) >= 16;
+        const int r = second ? max(min(key - 16, e1.hi), e1.lo) : max(min(key, e0.hi), e0.lo);
+        const uint32_t off = (uint32_t)(r * HD * ES + (lane % CH) * 16);
+        vf[it] = *reinterpret_cast<const u32x4_t*>((second ? e1.b : e0.b) + off);
+      }
+      return;
+    }
     const int cl = ctx - 1 - kt;
     const bool bvalid = cl >= 16;
     const char* b0 = half_base(p.vc, pa, kt);
@@ -286,6 +341,16 @@ __global__ void __launch_bounds__(512) attn_kernel(const AttnParams p) {
           s[hf * 4 + r] = v;
           tmax = fmaxf(tmax, v);
         }
+      if constexpr (WIN) {
+        if (k0t < kmax - p.window) {     // wave-uniform: a tile below the last row's left edge hides keys of some row
+          tmax = -INFINITY;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            if (k0t + (i >> 2) * 16 + g4 * 4 + (i & 3) < lim[rt] - p.window) s[i] = -INFINITY;
+            tmax = fmaxf(tmax, s[i]);
+          }
+        }
+      }
       tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
       tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
       const float mnew = fmaxf(m[rt], tmax);
@@ -501,10 +566,10 @@ __global__ void attn_combine_kernel(const float* __restrict__ ws_o, const float*
   }
 }
 
-template <int HD, int RT, int KT, bool KV8>
+template <int HD, int RT, int KT, bool KV8, bool WIN>
 static int attn_launch_rt(const AttnParams& p, dim3 grid, int waves, hipStream_t st) {
   const int lds = waves * attn_region_bytes<HD, RT>();
-  auto kern = attn_kernel<HD, RT, KT, false, KV8>;
+  auto kern = attn_kernel<HD, RT, KT, false, KV8, WIN>;
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
     return SSD_ERR_LAUNCH;
@@ -514,7 +579,7 @@ static int attn_launch_rt(const AttnParams& p, dim3 grid, int waves, hipStream_t
 
 // Row tiles per workgroup: two for prefill-sized query blocks (> 8 tiles; K/V bytes shared by 32 rows), one for the decode-side
 // shapes (more workgroups: the scan is bound by per-CU load bandwidth and latency, not by K/V bytes).
-template <int HD, bool KV8>
+template <int HD, bool KV8, bool WIN>
 static int attn_launch(const AttnParams& p, int B, int T, int max_q, int waves, int force_rt1, hipStream_t st) {
   const int G = p.nh / p.nkv;
   const int row_tiles = (max_q * G + 15) / 16;
@@ -524,7 +589,7 @@ static int attn_launch(const AttnParams& p, int B, int T, int max_q, int waves, 
   dim3 grid(B * p.nkv, (row_tiles + rt - 1) / rt, p.splits);
   // one key tile in flight per wave (KT = 1): measured on MI355X, KT = 2/4 buy nothing -- with 8 waves per workgroup
   // the scan is bound by the handful of CUs it occupies, not by a single wave's load latency
-  const int rc = rt == 2 ? attn_launch_rt<HD, 2, 1, KV8>(p, grid, waves, st) : attn_launch_rt<HD, 1, 1, KV8>(p, grid, waves, st);
+  const int rc = rt == 2 ? attn_launch_rt<HD, 2, 1, KV8, WIN>(p, grid, waves, st) : attn_launch_rt<HD, 1, 1, KV8, WIN>(p, grid, waves, st);
   if (rc != SSD_OK) return rc;
   if (p.splits > 1) {
     hipLaunchKernelGGL((attn_combine_kernel<HD>), dim3(T * p.nh), dim3(HD / 4), 0, st, p.ws_o, p.ws_ml, p.splits, p.nh,
@@ -559,7 +624,7 @@ extern "C" int ssd_attn_oproj_parts(const void* q_rows, const void* k_cache, con
   p.splits = 1; p.use_tr = 1; p.p_split = 1;
   p.scale_log2e = scale * 1.4426950408889634f;
   p.ow = (const u32x4_t*)w_o_frag; p.oparts = (float*)parts; p.oN = N;
-  p.k_scale = nullptr; p.v_scale = nullptr;
+  p.k_scale = nullptr; p.v_scale = nullptr; p.window = 0;
   const dim3 grid(nkv * (N / 128), 1, 1), block(512);
   hipStream_t st = (hipStream_t)stream;
   const int rt = rows > 16 ? 2 : 1;
@@ -578,13 +643,13 @@ extern "C" int ssd_attn_oproj_parts(const void* q_rows, const void* k_cache, con
   return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
 }
 
-template <bool KV8>
+template <bool KV8, bool WIN = false>
 static int attn_paged_impl(const void* q_rows, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale,
                            const int32_t* block_tables, int max_blocks, const int32_t* context_lens,
                            const int32_t* cu_q, int q_per_seq, int B, int T, int max_q, int nh, int nkv, int hd,
                            int block_size, float scale, int mode, int tree_K, int tree_mq, int tree_step,
                            int tree_F, const int32_t* tree_jidx, int splits, int flags, void* ws_o, void* ws_ml,
-                           void* out_rows, void* out_frag, void* stream) {
+                           void* out_rows, void* out_frag, void* stream, int window = 0) {
   if (B <= 0 || T <= 0 || max_q <= 0 || nh <= 0 || nkv <= 0 || nh % nkv) return SSD_ERR_SHAPE;
   if (hd != 64 && hd != 128) return SSD_ERR_SHAPE;
   if (block_size < 16 || (block_size & (block_size - 1)) != 0 || max_blocks <= 0) return SSD_ERR_SHAPE;
@@ -603,6 +668,7 @@ static int attn_paged_impl(const void* q_rows, const void* k_cache, const void* 
   p.scale_log2e = scale * 1.4426950408889634f;
   p.ow = nullptr; p.oparts = nullptr; p.oN = 0;
   p.k_scale = k_scale; p.v_scale = v_scale;
+  p.window = window < (1 << 30) ? window : (1 << 30);     // (lim - window stays an int; no context is that long)
   hipStream_t st = (hipStream_t)stream;
   // flags bits 8..11: waves per workgroup that split the key range and merge in LDS (default 1; 1..8)
   int waves = (flags >> 8) & 0xf;
@@ -610,7 +676,7 @@ static int attn_paged_impl(const void* q_rows, const void* k_cache, const void* 
   if (waves > 8) waves = 8;
   // flags bit 2: one 16-row tile per workgroup even for wider query blocks (twice the workgroups for the 24-branch tree)
   const int rt1 = (flags >> 2) & 1;
-  return hd == 128 ? attn_launch<128, KV8>(p, B, T, max_q, waves, rt1, st) : attn_launch<64, KV8>(p, B, T, max_q, waves, rt1, st);
+  return hd == 128 ? attn_launch<128, KV8, WIN>(p, B, T, max_q, waves, rt1, st) : attn_launch<64, KV8, WIN>(p, B, T, max_q, waves, rt1, st);
 }
 
 extern "C" int ssd_attn_paged(const void* q_rows, const void* k_cache, const void* v_cache,
@@ -643,6 +709,39 @@ extern "C" int ssd_attn_prefill_varlen_fp8(const void* q_rows, const void* k_cac
   if (!cu_q) return SSD_ERR_ARG;
   return ssd_attn_paged_fp8(q_rows, k_cache, v_cache, k_scale, v_scale, block_tables, max_blocks, context_lens, cu_q, 0, B, T, max_q, nh,
                             nkv, hd, block_size, scale, 0, 0, 0, 0, 1, nullptr, 1, 0, nullptr, nullptr, out_rows, out_frag, stream);
+}
+
+// ---- sliding window (include/ssd_hip_swa.h): the causal shapes of either cache type; window == 0 is the unwindowed entry itself ----
+extern "C" int ssd_attn_paged_window(const void* q_rows, const void* k_cache, const void* v_cache, const int32_t* block_tables,
+                                     int max_blocks, const int32_t* context_lens, const int32_t* cu_q, int q_per_seq, int B, int T,
+                                     int max_q, int nh, int nkv, int hd, int block_size, float scale, int mode, int tree_K, int tree_mq,
+                                     int tree_step, int tree_F, const int32_t* tree_jidx, int splits, int flags, void* ws_o,
+                                     void* ws_ml, void* out_rows, void* out_frag, int window, void* stream) {
+  if (window < 0 || (window > 0 && mode != 0)) return SSD_ERR_ARG;       // the tree mask is not windowed
+  if (window == 0)
+    return ssd_attn_paged(q_rows, k_cache, v_cache, block_tables, max_blocks, context_lens, cu_q, q_per_seq, B, T, max_q, nh, nkv, hd,
+                          block_size, scale, mode, tree_K, tree_mq, tree_step, tree_F, tree_jidx, splits, flags, ws_o, ws_ml, out_rows,
+                          out_frag, stream);
+  if (!q_rows || !k_cache || !v_cache || !block_tables || !context_lens || (!out_rows && !out_frag)) return SSD_ERR_ARG;
+  return attn_paged_impl<false, true>(q_rows, k_cache, v_cache, nullptr, nullptr, block_tables, max_blocks, context_lens, cu_q, q_per_seq,
+                                      B, T, max_q, nh, nkv, hd, block_size, scale, 0, 0, 0, 0, 1, nullptr, splits, flags, ws_o, ws_ml,
+                                      out_rows, out_frag, stream, window);
+}
+extern "C" int ssd_attn_paged_fp8_window(const void* q_rows, const void* k_cache, const void* v_cache, const float* k_scale,
+                                         const float* v_scale, const int32_t* block_tables, int max_blocks, const int32_t* context_lens,
+                                         const int32_t* cu_q, int q_per_seq, int B, int T, int max_q, int nh, int nkv, int hd,
+                                         int block_size, float scale, int mode, int tree_K, int tree_mq, int tree_step, int tree_F,
+                                         const int32_t* tree_jidx, int splits, int flags, void* ws_o, void* ws_ml, void* out_rows,
+                                         void* out_frag, int window, void* stream) {
+  if (window < 0 || (window > 0 && mode != 0)) return SSD_ERR_ARG;
+  if (window == 0)
+    return ssd_attn_paged_fp8(q_rows, k_cache, v_cache, k_scale, v_scale, block_tables, max_blocks, context_lens, cu_q, q_per_seq, B, T,
+                              max_q, nh, nkv, hd, block_size, scale, mode, tree_K, tree_mq, tree_step, tree_F, tree_jidx, splits, flags,
+                              ws_o, ws_ml, out_rows, out_frag, stream);
+  if (!q_rows || !k_cache || !v_cache || !block_tables || !context_lens || (!out_rows && !out_frag)) return SSD_ERR_ARG;
+  return attn_paged_impl<true, true>(q_rows, k_cache, v_cache, k_scale, v_scale, block_tables, max_blocks, context_lens, cu_q, q_per_seq,
+                                     B, T, max_q, nh, nkv, hd, block_size, scale, 0, 0, 0, 0, 1, nullptr, splits, flags, ws_o, ws_ml,
+                                     out_rows, out_frag, stream, window);
 }
 
 // The reference's two other attention call sites under their own names (SURVEY section 8b's list): thin forms of ssd_attn_paged, which already

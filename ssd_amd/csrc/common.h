@@ -23,6 +23,7 @@ constexpr int SSD_MAX_DEVICES = 16;  // per-device host-side caches (function at
 #include "ssd_hip_w4zp.h"
 #include "ssd_hip_mxfp4.h"
 #include "ssd_hip_kv8.h"
+#include "ssd_hip_swa.h"
 #include "ssd_hip_filter.h"
 #include "ssd_hip_penalty.h"
 #include "ssd_hip_logprob.h"

@@ -65,6 +65,9 @@ def hip_runner_factory(config, model_cfg, *, is_draft: bool, topo, **kw):
                        weights_seed=config.draft_weights_seed if is_draft else config.weights_seed, **kw)
 
 
+hip_runner_factory.supports_swa = True       # HipDecoder._attn launches ssd_attn_paged_window on a windowed layer
+
+
 class LLMEngine:
     def __init__(self, model: str, runner_factory=None, topology=None, inprocess_draft: bool = False, **kwargs):
         """inprocess_draft: run the async draft server inside this process over a loopback transport (same
@@ -100,6 +103,12 @@ class LLMEngine:
         if moe and self.topo.device.type != "cuda":
             raise ValueError(f"model={model!r} is a mixture-of-experts target: it needs the HIP runner on a GPU (there is no CPU oracle "
                              "for the family)")
+        # sliding-window models: refused before any runner is built unless the factory says its runners have the windowed kernel
+        # (the CPU oracle has no window: it would run full attention and answer with the wrong logits)
+        swa = config.hf_config.windowed or (config.speculate and config.draft_hf_config.windowed)
+        if swa and not getattr(factory, "supports_swa", False):
+            raise ValueError(f"model={model!r} has sliding-window layers (sliding_window={config.hf_config.sliding_window}): "
+                             f"{getattr(factory, '__name__', factory)} builds runners without the windowed attention kernel")
 
         self.draft_runner = None
         self.loras = None           # enable_lora: the registry of the adapter slots (ssd_amd/lora.py), else None

@@ -27,6 +27,7 @@ from ssd_amd.hip import w4_ops as W4
 from ssd_amd.hip import w4zp_ops as W4Z
 from ssd_amd.hip import mx4_ops as MX4
 from ssd_amd.hip import kv8_ops as KV8
+from ssd_amd.hip import swa_ops as SWA
 from ssd_amd.hip import lora_ops as LO
 from ssd_amd.hip import moe_ops as MOE
 from ssd_amd import lora as LR
@@ -196,7 +197,14 @@ class HipDecoder:
         self.pf_parts = True
         if self.quantized or self.moe:
             self.use_parts = self.fuse_attn_o = self.pf_parts = False
-        if self.kv8:
+        # a model with any sliding-window layer (cfg.windowed; include/ssd_hip_swa.h) gives up the routes that run attention inside
+        # another kernel -- attention + o_proj here, the chain and tree segments below -- as the fp8-KV target does; the QKV epilogue
+        # (RoPE + KV store) does not read the cache and stays
+        self.swa = cfg.windowed
+        if self.swa and cfg.head_dim not in (64, 128):
+            raise ValueError(f"sliding-window attention needs head_dim 64 or 128, got {cfg.head_dim}")
+        assert not self.swa or (tp_size == 1 and not force_collectives and taps is None), "sliding-window models are single-rank, without taps"
+        if self.kv8 or self.swa:
             self.fuse_attn_o = False
         # fp8 KV: scale and inverse-scale tables fp32 [L][2 (K | V)][nkv], allocated once (hipGraphs bake the pointers)
         self.kv_scale = torch.ones(cfg.num_layers, 2, self.nkv, dtype=torch.float32, device=device) if self.kv8 else None
@@ -211,7 +219,7 @@ class HipDecoder:
         _geo = (self.h, self.qn, self.I, self.qkv_n, self.hd)
         _validated = _geo == (2048, 2048, 8192, 3072, 64)
         self.chain_seg = ((_cs == "1" or (_cs == "auto" and _validated)) and not cfg.qk_norm and tp_size == 1 and not self.use_coll and not self.quantized
-                          and not self.moe and not self.kv8 and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
+                          and not self.moe and not self.kv8 and not self.swa and taps is None and H.chain_segment_ok(self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         # the same segment for 2..30 token rows (csrc/tree_segment.hip): attention + ONE resident launch per layer instead of 7
         # launches.  Measured on MI355X at the 1B draft's geometry (profiles/r05_tree_seg_probe_v1.txt, parity tests/test_hip_tree_segment.py):
         # the K+1 = 8-row glue decode 0.945 -> 0.857 ms (kept), the 24-row tree step 0.943 -> 0.965 ms (NOT kept: at 24 rows every
@@ -227,7 +235,7 @@ class HipDecoder:
         #  is all there is: tree step 1.248 -> 1.240 ms at 6 rows, 1.275 -> 1.299 at 12, 1.363 -> 1.457 at 24,
         #  profiles/r05_tree_seg_probe_qwen.txt -- so "auto" leaves it off there)
         self.tree_seg = ((_ts == "1" or (_ts == "auto" and _validated)) and tp_size == 1 and not self.use_coll and not self.quantized
-                         and not self.moe and not self.kv8 and taps is None and max_tokens >= 2
+                         and not self.moe and not self.kv8 and not self.swa and taps is None and max_tokens >= 2
                          and H.tree_segment_ok(2, self.h, self.qn, self.I, self.qkv_n, self.nh, self.nkv, self.hd))
         if self.chain_seg:
             self.chain_gr = z(H.chain_granule_bytes(self.h, self.I) // 8, dtype=torch.int64)
@@ -629,6 +637,20 @@ class HipDecoder:
         """The layer's paged attention launch into buf_af, over the bf16 or the fp8 cache.  flags None: left to the kernel's default
         (0: the chain / tree segments and the EAGLE-3 draft, which never take forward()'s _attn_flags)."""
         fl = {} if flags is None else dict(flags=flags)
+        window = self.cfg.window_of(li)
+        if window:
+            # a windowed layer (include/ssd_hip_swa.h): the same launch over the last `window` keys of every row, its key splits sized
+            # from what it scans
+            assert meta.mode == H.MODE_CAUSAL, "the draft-tree mask is not windowed"
+            kw = dict(cu_q=meta.cu_q, q_per_seq=meta.q_per_seq, splits=self._attn_cfg(T, meta, window)[0], ws_o=self.ws_o, ws_ml=self.ws_ml,
+                      out_frag=self.buf_af, waves=waves, window=window, **fl)
+            args = (self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks, meta.context_lens, meta.B, T,
+                    meta.max_q, self.nh, self.nkv, self.hd, self.block_size, scale)
+            if self.kv8:
+                SWA.attn_paged_fp8_window(*args, k_scale=self.kv_scale[li, 0], v_scale=self.kv_scale[li, 1], **kw)
+            else:
+                SWA.attn_paged_window(*args, **kw)
+            return
         if self.kv8:
             assert meta.mode == H.MODE_CAUSAL, "the fp8 KV cache serves the target's causal shapes only"
             KV8.attn_paged_fp8(self.buf_q, self.kv_cache[li, 0], self.kv_cache[li, 1], meta.block_tables, self.max_blocks,
@@ -755,7 +777,7 @@ class HipDecoder:
             b *= 2
         return b
 
-    def _attn_cfg(self, T: int, meta: AttnMeta) -> tuple[int, int]:
+    def _attn_cfg(self, T: int, meta: AttnMeta, window: int = 0) -> tuple[int, int]:
         """(grid key-splits, waves per workgroup).  Up to 8 waves of one workgroup split the key range and merge
         in LDS (one launch).  A decode-side launch occupies only B*nkv*row_tiles CUs and each CU sustains a few
         tens of GB/s of K/V loads, so beyond ~1K keys per workgroup the scan is spread over more workgroups with
@@ -772,6 +794,8 @@ class HipDecoder:
         # (prefill with 4 / 8 waves per workgroup, measured on c4: TTFT 30.92 ms (this heuristic, 2 waves) / 30.68 / 30.74 -- within noise, and
         #  another accumulation order: not adopted, the override switch retired in round 5)
         ctx = self.ctx_bucket(meta.ctx_hint if meta.ctx_hint > 0 else self.max_model_len)
+        if window:      # a windowed layer scans at most window + max_q keys per workgroup, whatever the context (32k under 4k: 8 splits, not 16)
+            ctx = min(ctx, window + meta.max_q)
         splits = 1 if ctx <= 1024 else max(1, min(self.max_splits, ctx // 512))
         if base >= 256 or T > self.max_split_tokens:
             splits = 1

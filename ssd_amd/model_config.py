@@ -38,6 +38,25 @@ class ModelConfig:
     num_experts_per_tok: int = 0
     moe_intermediate_size: int = 0
     norm_topk_prob: bool = False
+    # Sliding-window attention (include/ssd_hip_swa.h): the query at position i sees the keys j with i - W < j <= i.  sliding_window
+    # = W for every layer (0: full causal attention); layer_windows, when not empty, has one entry per layer and overrides it
+    # (0 = a full layer): the alternating local / global layers of a layer_types list.
+    sliding_window: int = 0
+    layer_windows: tuple = ()
+
+    def window_of(self, li: int) -> int:
+        return self.layer_windows[li] if self.layer_windows else self.sliding_window
+
+    @property
+    def windowed(self) -> bool:
+        return any(self.layer_windows) if self.layer_windows else self.sliding_window != 0
+
+    def check_windows(self) -> None:
+        if self.layer_windows and len(self.layer_windows) != self.num_layers:
+            raise ValueError(f"layer_windows has {len(self.layer_windows)} entries for num_layers={self.num_layers}")
+        bad = [w for w in (self.sliding_window, *self.layer_windows) if isinstance(w, bool) or not isinstance(w, int) or w < 0]
+        if bad:
+            raise ValueError(f"sliding_window must be an integer >= 1 where a layer is windowed (0 = a full layer), got {bad[0]!r}")
 
     @property
     def q_size(self) -> int:
@@ -54,7 +73,7 @@ class ModelConfig:
     def from_hf(hf) -> "ModelConfig":
         """From a transformers config object (or anything with the same attributes)."""
         mt = getattr(hf, "model_type", "llama")
-        family = "qwen3" if "qwen" in mt else "llama"
+        family = "qwen3" if "qwen" in mt else "llama"       # ("mistral": Llama's layer and tensor names + its window)
         moe = {}
         if mt == "qwen3_moe":
             family = "qwen3_moe"
@@ -94,7 +113,34 @@ class ModelConfig:
             attention_bias=bool(getattr(hf, "attention_bias", False)),
             draft_vocab_size=int(getattr(hf, "draft_vocab_size", 0) or 0),
             **moe,
+            **_windows_from_hf(hf, mt),
         )
+
+
+def _windows_from_hf(hf, mt: str) -> dict:
+    """sliding_window / layer_windows of a transformers config: an explicit layer_types list ("sliding_attention" / "full_attention")
+    wins; without one a Qwen config windows the layers with index >= max_window_layers unless use_sliding_window is false
+    (transformers' Qwen2Config / Qwen3Config), and every other family (Mistral) windows every layer."""
+    W = getattr(hf, "sliding_window", None)
+    W = 0 if W is None else int(W)
+    L = hf.num_hidden_layers
+    types = getattr(hf, "layer_types", None)
+    if types is None:
+        if "qwen" not in mt:
+            types = ["sliding_attention" if W else "full_attention"] * L
+        else:
+            on = bool(getattr(hf, "use_sliding_window", False)) and W != 0
+            first = getattr(hf, "max_window_layers", L)
+            types = ["sliding_attention" if on and li >= first else "full_attention" for li in range(L)]
+    types = list(types)
+    if len(types) != L or set(types) - {"sliding_attention", "full_attention"}:
+        raise ValueError(f"layer_types must name 'sliding_attention' or 'full_attention' for each of the {L} layers, got {types!r}")
+    n = types.count("sliding_attention")
+    if n and W < 1:
+        raise ValueError(f"layer_types has {n} sliding_attention layers but sliding_window={getattr(hf, 'sliding_window', None)!r}")
+    if n == 0:
+        return {}
+    return dict(sliding_window=W) if n == L else dict(sliding_window=W, layer_windows=tuple(W if t == "sliding_attention" else 0 for t in types))
 
 
 # Public shapes of the models BASELINE.json names (SURVEY.md A.1; no weights exist offline).
@@ -129,6 +175,12 @@ MOE_PRESETS = {
 }
 
 
+# Sliding-window targets (public config.json shapes), a side table for the same reason.
+SWA_PRESETS = {
+    "mistral-7b-v0.1": ModelConfig("llama", 4096, 32, 32, 8, 128, 14336, 32000, 1e-5, 1e4, 32768, False, sliding_window=4096),
+}
+
+
 def presets() -> dict:
-    """The one registry of preset names: PRESETS and MOE_PRESETS together (iterate or look up here, not in either dictionary)."""
-    return {**PRESETS, **MOE_PRESETS}
+    """The one registry of preset names: PRESETS, MOE_PRESETS and SWA_PRESETS together (iterate or look up here, not in any one dictionary)."""
+    return {**PRESETS, **MOE_PRESETS, **SWA_PRESETS}
