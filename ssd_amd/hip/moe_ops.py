@@ -1,5 +1,5 @@
 """ctypes table and torch front end of the mixture-of-experts entry points (include/ssd_hip_moe.h, include/ssd_hip_moe_mxfp4.h,
-include/ssd_hip_moe_fp8b.h).
+include/ssd_hip_moe_fp8b.h, include/ssd_hip_moe_tiled.h).
 
 Kept apart from ``lib.SIGNATURES`` and the other additive tables: these bind on the same libssdhip.so.  As in ops.py, nothing here
 computes in torch; the calls enqueue on the current stream and are hipGraph-capturable.  The expert tables are laid out by
@@ -36,6 +36,12 @@ MOE_FP8B_SIGNATURES = {
     "ssd_moe_gemm_fp8b": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
 }
 
+# name -> argtypes, exactly include/ssd_hip_moe_tiled.h
+MOE_TILED_SIGNATURES = {
+    "ssd_moe_gemm_tiled": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+}
+TILED_BM = 128
+
 
 def load_moe_library():
     return bind(MOE_SIGNATURES)
@@ -49,6 +55,10 @@ def load_moe_fp8b_library():
     return bind(MOE_FP8B_SIGNATURES)
 
 
+def load_moe_tiled_library():
+    return bind(MOE_TILED_SIGNATURES)
+
+
 def moe_route(logits, ld: int, T: int, E: int, k: int, norm: bool, topk_ids, topk_w, offs, perm):
     """Top-k experts and routing weights of the bf16 router-logit rows [T][ld], and the grouping tables offs [E + 1] / perm [T k]."""
     _check(load_moe_library().ssd_moe_route(_p(logits), ld, T, E, k, 1 if norm else 0, _p(topk_ids), _p(topk_w), _p(offs), _p(perm),
@@ -60,6 +70,12 @@ def moe_gemm(rows_in, w_frag, offs, perm, out, T: int, k: int, E: int, N: int, K
     act [T k][K] -> d [T k][N]."""
     _check(load_moe_library().ssd_moe_gemm(_p(rows_in), _p(w_frag), _p(offs), _p(perm), _p(out), T, k, E, N, K, epilogue, _stream()),
            "ssd_moe_gemm")
+
+
+def moe_gemm_tiled(rows_in, w_frag, offs, perm, out, T: int, k: int, E: int, N: int, K: int, epilogue: int):
+    """moe_gemm on the compute-bound LDS-tiled kernel (long prefills): the same arguments and tables."""
+    _check(load_moe_tiled_library().ssd_moe_gemm_tiled(_p(rows_in), _p(w_frag), _p(offs), _p(perm), _p(out), T, k, E, N, K, epilogue,
+                                                       _stream()), "ssd_moe_gemm_tiled")
 
 
 def moe_gemm_mxfp4(rows_in, q_frag, s_frag, offs, perm, out, T: int, k: int, E: int, N: int, K: int, epilogue: int):

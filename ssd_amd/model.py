@@ -394,6 +394,8 @@ class HipDecoder:
             MOE.moe_gemm_mxfp4(rows_in, self.w[name], self.w[name + "_scale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
         elif self.fp8:
             MOE.moe_gemm_fp8b(rows_in, self.w[name], self.w[name + "_bscale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
+        elif T >= self.MOE_TILED_MIN_T:
+            MOE.moe_gemm_tiled(rows_in, self.w[name], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
         else:
             MOE.moe_gemm(rows_in, self.w[name], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
 
@@ -679,6 +681,9 @@ class HipDecoder:
     FP8_DIRECT_MAX_T = 128
     # w4a16 linears of up to this many rows run on the w4a16 GEMM itself; longer prompts dequantize into self._deq first
     W4_DIRECT_MAX_T = 128
+    # bf16 expert GEMMs of at least this many rows run on the compute-bound tiled kernel (csrc/moe_tiled.hip); shorter forwards stay
+    # on the weight-streaming one (csrc/moe.hip).  Measured: the table in DESIGN.md "Tiled expert GEMM"
+    MOE_TILED_MIN_T = 512
     # mxfp4 linears of up to this many rows run on the mxfp4 GEMM itself; longer prompts dequantize into self._deq first
     MX4_DIRECT_MAX_T = 128
 
