@@ -8,8 +8,18 @@
 // fragment tiles, and lane l of a token tile copies the 16 bytes moe.hip loads into its B register (row perm[..], column
 // 32 kt + 8 (l >> 4)) -- the DMA's global address is per lane, its LDS address lane-linear, so the gather costs no register and no
 // ds_write.  Two LDS buffers of one 64-deep K stage each, one raw s_barrier per stage (gemm_lm_kernel's pipeline).
+//
+// MX4 = true is the same kernel over "mx4 frag" expert tables (include/ssd_hip_moe_tiled_mxfp4.h).  The LDS-DMA cannot widen, so the
+// table operand alone goes through registers: per 128-column unit a wave holds, for each of its GW row groups, the lane's 16-byte code
+// chunk and 4-byte scale quad (moe_mxfp4.hip's A-operand loads), widens two of the four code words per 64-deep stage with
+// v_cvt_scalef32_pk_bf16_fp4 and writes the two k-tiles lane-linear (ds_write_b128) into the LDS slots the bf16 kernel's DMA fills.
+// A unit is two stages: words 0, 1 then words 2, 3 of the codes in registers; the next unit's codes are loaded into the same registers
+// right after the second half is written, ahead of that stage's MFMAs.  Everything else -- work unit, grid, prefix sum, token gather,
+// MFMA loop, epilogues, clamps -- is the code below, once.
 #include "common.h"
+#include "mx4.h"
 #include "ssd_hip_moe_tiled.h"
+#include "ssd_hip_moe_tiled_mxfp4.h"
 
 typedef __attribute__((address_space(1))) void* mt_gptr_t;
 typedef __attribute__((address_space(3))) void* mt_lptr_t;
@@ -17,10 +27,12 @@ typedef __attribute__((address_space(3))) void* mt_lptr_t;
 // grid (nb * spans): workgroup id -> (span, block b of the bound nb = T k / BM + E), blocks fastest.  WM x WN waves; wave (wm, wn)
 // owns the span's row groups wn NTW .. + NTW and the block's token tiles wm, wm + WM, ... (dealt round-robin, so a ragged block's
 // tiles spread over the wm).
-template <int EPI, int BM, int BN, int WM, int WN>
+// Wf: the bf16 fragment tables, or (MX4) the code tables with their scale quads in Sf.
+template <int EPI, int BM, int BN, int WM, int WN, bool MX4>
 __global__ void __launch_bounds__(64 * WM * WN, WM * WN <= 4 ? 2 : 1)
-moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, const int32_t* __restrict__ offs,
-                 const int32_t* __restrict__ perm, bf16_t* __restrict__ out, int T, int k, int E, int N, int K, int nb) {
+moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, const uint32_t* __restrict__ Sf,
+                 const int32_t* __restrict__ offs, const int32_t* __restrict__ perm, bf16_t* __restrict__ out, int T, int k, int E, int N,
+                 int K, int nb) {
   constexpr int NW = WM * WN;
   constexpr int TW = BN / 16, TX = BM / 16, TT = TW + TX;      // fragment tiles per k-tile: table groups first, then token tiles
   constexpr int GW = TW / NW, GX = TX / NW;                    // tiles of each kind a wave stages per k-tile
@@ -74,11 +86,17 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
 
   // ---- staging: wave v copies row groups v GW .. and token tiles v GX .. of both k-tiles of a stage ----
   const u32x4_t* wsrc[GW];
+  const uint32_t* ssrc[GW];
   const bf16_t* xsrc[GX];
 #pragma unroll
   for (int i = 0; i < GW; ++i) {
     const int grp = min(g0 + wave * GW + i, NG - 1);           // groups past the table (the last span): clamped, never stored
-    wsrc[i] = Wf + ((((size_t)e * NG + grp) * KT) << 6) + lane;
+    if constexpr (MX4) {                                       // a unit of 4 k-tiles is one code chunk and one scale quad per lane
+      wsrc[i] = Wf + ((((size_t)e * NG + grp) * (KT >> 2)) << 6) + lane;
+      ssrc[i] = Sf + ((((size_t)e * NG + grp) * (KT >> 2)) << 4) + (lane & 15);
+    } else {
+      wsrc[i] = Wf + ((((size_t)e * NG + grp) * KT) << 6) + lane;
+    }
   }
 #pragma unroll
   for (int i = 0; i < GX; ++i) {
@@ -98,11 +116,32 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
       if (wave * GX + i < xtv)
         __builtin_amdgcn_global_load_lds((mt_gptr_t)(xsrc[i] + (size_t)kt * 32), (mt_lptr_t)&lds[buf][ks][TW + wave * GX + i][0], 16, 0, 0);
   };
-  auto issue = [&](int kb, int buf) {
+  // MX4: the codes and scale quads of the unit being staged, and the widening of code words 2 HALF, 2 HALF + 1 into the two k-tiles
+  // of a stage (K % 128 == 0: a stage is half a unit, never ragged)
+  u32x4_t qc[GW];
+  uint32_t sc[GW];
+  auto load_q = [&](int c) {
+#pragma unroll
+    for (int i = 0; i < GW; ++i) {
+      qc[i] = __builtin_nontemporal_load(wsrc[i] + ((size_t)c << 6));
+      sc[i] = __builtin_nontemporal_load(ssrc[i] + ((size_t)c << 4));
+    }
+  };
+  auto widen = [&](auto half, int buf) {
+    constexpr int HALF = decltype(half)::value;
+#pragma unroll
+    for (int i = 0; i < GW; ++i)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) lds[buf][ks][wave * GW + i][lane] = mx4_to_bf16(qc[i][2 * HALF + ks], mx4_scale(sc[i], 2 * HALF + ks));
+  };
+  auto issue = [&](int kb, int buf) {                          // the DMA of stage kb
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const int kt = 2 * kb + ks;
-      if (kt < KT) { stage_w(kt, buf, ks); stage_x(kt, buf, ks); }
+      if (kt < KT) {
+        if constexpr (!MX4) stage_w(kt, buf, ks);
+        stage_x(kt, buf, ks);
+      }
     }
   };
 
@@ -113,11 +152,14 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
     for (int mt = 0; mt < MTW; ++mt) acc[nt][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int nkb = (KT + 1) >> 1;
+  if constexpr (MX4) load_q(0);
   issue(0, 0);
+  if constexpr (MX4) widen(std::integral_constant<int, 0>{}, 0);
   for (int kb = 0; kb < nkb; ++kb) {
     const int cur = kb & 1;
     // RAW: this wave's DMA of stage kb has landed, and after the barrier every wave's has.  WAR: every wave finished reading buffer
-    // cur ^ 1 (stage kb - 1) before the barrier, so it may be restaged right after it.
+    // cur ^ 1 (stage kb - 1) before the barrier, so it may be restaged right after it.  MX4: lgkmcnt(0) is the same RAW for the widened
+    // tiles' ds_writes, and vmcnt(0) also lands the next unit's codes in their registers.
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -137,6 +179,19 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
 #pragma unroll
           for (int nt = 0; nt < NTW; ++nt) acc[nt][mt] = mfma16(a[nt], bt[mt], acc[nt][mt]);
         }
+      if constexpr (MX4) {
+        // behind the first k-tile's MFMAs, which run on while the VALU widens: stage kb + 1 is the second half of this unit (kb
+        // even; once it is written the registers take the next unit's codes) or the first half of the next unit (kb odd), whose
+        // codes the vmcnt(0) above landed
+        if (ks == 0 && kb + 1 < nkb) {
+          if (kb & 1) {
+            widen(std::integral_constant<int, 0>{}, cur ^ 1);
+          } else {
+            widen(std::integral_constant<int, 1>{}, cur ^ 1);
+            if (2 * kb + 4 < KT) load_q((kb >> 1) + 1);
+          }
+        }
+      }
     }
   }
 
@@ -177,28 +232,45 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-template <int EPI, int BM, int BN, int WM, int WN>
-static int tiled_go(const void* rows_in, const void* w_frag, const int32_t* offs, const int32_t* perm, void* out, int T, int k, int E,
-                    int N, int K, hipStream_t st) {
+template <int EPI, int BM, int BN, int WM, int WN, bool MX4>
+static int tiled_go(const void* rows_in, const void* w_frag, const void* s_frag, const int32_t* offs, const int32_t* perm, void* out, int T,
+                    int k, int E, int N, int K, hipStream_t st) {
   // sum_e ceil(n_e / BM) <= floor(T k / BM) + E: a grid that depends on no device data
   const long nb = (long)T * k / BM + E, spans = (N + BN - 1) / BN;
   if (nb * spans > 0x7fffffffL) return SSD_ERR_SHAPE;
-  hipLaunchKernelGGL((moe_tiled_kernel<EPI, BM, BN, WM, WN>), dim3((unsigned)(nb * spans)), dim3(64 * WM * WN), 0, st,
-                     (const bf16_t*)rows_in, (const u32x4_t*)w_frag, offs, perm, (bf16_t*)out, T, k, E, N, K, (int)nb);
+  hipLaunchKernelGGL((moe_tiled_kernel<EPI, BM, BN, WM, WN, MX4>), dim3((unsigned)(nb * spans)), dim3(64 * WM * WN), 0, st,
+                     (const bf16_t*)rows_in, (const u32x4_t*)w_frag, (const uint32_t*)s_frag, offs, perm, (bf16_t*)out, T, k, E, N, K,
+                     (int)nb);
   return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
+}
+
+// both entries' checks and launch; s_frag is null for bf16 tables
+template <bool MX4>
+static int tiled_entry(const void* rows_in, const void* w_frag, const void* s_frag, const int32_t* offs, const int32_t* perm, void* out,
+                       int T, int k, int E, int N, int K, int epilogue, void* stream) {
+  if (!rows_in || !w_frag || (MX4 && !s_frag) || !offs || !perm || !out) return SSD_ERR_ARG;
+  if (epilogue != SSD_MOE_EPI_UP && epilogue != SSD_MOE_EPI_DOWN) return SSD_ERR_ARG;
+  if (T <= 0 || k < 1 || k > SSD_MOE_MAX_K || E < SSD_MOE_MIN_E || E > SSD_MOE_MAX_E || (E & 7) || k > E) return SSD_ERR_SHAPE;
+  if ((long)T * k > (1L << 24)) return SSD_ERR_SHAPE;
+  if (K <= 0 || (K & (MX4 ? 127 : 31)) || N <= 0) return SSD_ERR_SHAPE;
+  if (epilogue == SSD_MOE_EPI_UP ? (N & 63) : (N & 15)) return SSD_ERR_SHAPE;
+  // 128 entries x 128 table rows, 2 x 2 waves (64 KiB LDS: two workgroups per CU).  A 256 x 128 form with 4 x 2 waves was measured
+  // and lost at every T (DESIGN.md "Tiled expert GEMM"): an expert's ragged last block leaves more of a larger workgroup idle
+  // The mx4 form keeps that shape and the 64-deep stage: a unit is widened in two halves from codes held in registers, so LDS stays
+  // 64 KiB and two workgroups share a CU (DESIGN.md "Tiled expert GEMM over MXFP4 tables")
+  if (epilogue == SSD_MOE_EPI_UP)
+    return tiled_go<SSD_MOE_EPI_UP, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2, MX4>(rows_in, w_frag, s_frag, offs, perm, out, T, k, E, N, K,
+                                                                                   (hipStream_t)stream);
+  return tiled_go<SSD_MOE_EPI_DOWN, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2, MX4>(rows_in, w_frag, s_frag, offs, perm, out, T, k, E, N, K,
+                                                                                   (hipStream_t)stream);
 }
 
 extern "C" int ssd_moe_gemm_tiled(const void* rows_in, const void* w_frag, const int32_t* offs, const int32_t* perm, void* out, int T,
                                   int k, int E, int N, int K, int epilogue, void* stream) {
-  if (!rows_in || !w_frag || !offs || !perm || !out) return SSD_ERR_ARG;
-  if (epilogue != SSD_MOE_EPI_UP && epilogue != SSD_MOE_EPI_DOWN) return SSD_ERR_ARG;
-  if (T <= 0 || k < 1 || k > SSD_MOE_MAX_K || E < SSD_MOE_MIN_E || E > SSD_MOE_MAX_E || (E & 7) || k > E) return SSD_ERR_SHAPE;
-  if ((long)T * k > (1L << 24)) return SSD_ERR_SHAPE;
-  if (K <= 0 || (K & 31) || N <= 0) return SSD_ERR_SHAPE;
-  if (epilogue == SSD_MOE_EPI_UP ? (N & 63) : (N & 15)) return SSD_ERR_SHAPE;
-  // 128 entries x 128 table rows, 2 x 2 waves (64 KiB LDS: two workgroups per CU).  A 256 x 128 form with 4 x 2 waves was measured
-  // and lost at every T (DESIGN.md "Tiled expert GEMM"): an expert's ragged last block leaves more of a larger workgroup idle
-  if (epilogue == SSD_MOE_EPI_UP)
-    return tiled_go<SSD_MOE_EPI_UP, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2>(rows_in, w_frag, offs, perm, out, T, k, E, N, K, (hipStream_t)stream);
-  return tiled_go<SSD_MOE_EPI_DOWN, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2>(rows_in, w_frag, offs, perm, out, T, k, E, N, K, (hipStream_t)stream);
+  return tiled_entry<false>(rows_in, w_frag, nullptr, offs, perm, out, T, k, E, N, K, epilogue, stream);
+}
+
+extern "C" int ssd_moe_gemm_tiled_mxfp4(const void* rows_in, const void* q_frag, const void* s_frag, const int32_t* offs,
+                                        const int32_t* perm, void* out, int T, int k, int E, int N, int K, int epilogue, void* stream) {
+  return tiled_entry<true>(rows_in, q_frag, s_frag, offs, perm, out, T, k, E, N, K, epilogue, stream);
 }

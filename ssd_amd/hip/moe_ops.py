@@ -1,5 +1,5 @@
 """ctypes table and torch front end of the mixture-of-experts entry points (include/ssd_hip_moe.h, include/ssd_hip_moe_mxfp4.h,
-include/ssd_hip_moe_fp8b.h, include/ssd_hip_moe_tiled.h).
+include/ssd_hip_moe_fp8b.h, include/ssd_hip_moe_tiled.h, include/ssd_hip_moe_tiled_mxfp4.h).
 
 Kept apart from ``lib.SIGNATURES`` and the other additive tables: these bind on the same libssdhip.so.  As in ops.py, nothing here
 computes in torch; the calls enqueue on the current stream and are hipGraph-capturable.  The expert tables are laid out by
@@ -42,6 +42,11 @@ MOE_TILED_SIGNATURES = {
 }
 TILED_BM = 128
 
+# name -> argtypes, exactly include/ssd_hip_moe_tiled_mxfp4.h
+MOE_TILED_MX4_SIGNATURES = {
+    "ssd_moe_gemm_tiled_mxfp4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+}
+
 
 def load_moe_library():
     return bind(MOE_SIGNATURES)
@@ -57,6 +62,10 @@ def load_moe_fp8b_library():
 
 def load_moe_tiled_library():
     return bind(MOE_TILED_SIGNATURES)
+
+
+def load_moe_tiled_mx4_library():
+    return bind(MOE_TILED_MX4_SIGNATURES)
 
 
 def moe_route(logits, ld: int, T: int, E: int, k: int, norm: bool, topk_ids, topk_w, offs, perm):
@@ -82,6 +91,12 @@ def moe_gemm_mxfp4(rows_in, q_frag, s_frag, offs, perm, out, T: int, k: int, E: 
     """moe_gemm over E MXFP4 tables [N][K]: q_frag E * N * K / 2 bytes of mx4 frag codes, s_frag E * N * K / 32 scale bytes."""
     _check(load_moe_mx4_library().ssd_moe_gemm_mxfp4(_p(rows_in), _p(q_frag), _p(s_frag), _p(offs), _p(perm), _p(out), T, k, E, N, K,
                                                      epilogue, _stream()), "ssd_moe_gemm_mxfp4")
+
+
+def moe_gemm_tiled_mxfp4(rows_in, q_frag, s_frag, offs, perm, out, T: int, k: int, E: int, N: int, K: int, epilogue: int):
+    """moe_gemm_mxfp4 on the compute-bound LDS-tiled kernel (long prefills): the same arguments and tables."""
+    _check(load_moe_tiled_mx4_library().ssd_moe_gemm_tiled_mxfp4(_p(rows_in), _p(q_frag), _p(s_frag), _p(offs), _p(perm), _p(out), T, k, E,
+                                                                 N, K, epilogue, _stream()), "ssd_moe_gemm_tiled_mxfp4")
 
 
 def moe_gemm_fp8b(rows_in, q_frag, s_grp, offs, perm, out, T: int, k: int, E: int, N: int, K: int, epilogue: int):
