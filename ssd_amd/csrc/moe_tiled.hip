@@ -9,30 +9,45 @@
 // 32 kt + 8 (l >> 4)) -- the DMA's global address is per lane, its LDS address lane-linear, so the gather costs no register and no
 // ds_write.  Two LDS buffers of one 64-deep K stage each, one raw s_barrier per stage (gemm_lm_kernel's pipeline).
 //
-// MX4 = true is the same kernel over "mx4 frag" expert tables (include/ssd_hip_moe_tiled_mxfp4.h).  The LDS-DMA cannot widen, so the
+// FMT = MT_MX4 is the same kernel over "mx4 frag" expert tables (include/ssd_hip_moe_tiled_mxfp4.h).  The LDS-DMA cannot widen, so the
 // table operand alone goes through registers: per 128-column unit a wave holds, for each of its GW row groups, the lane's 16-byte code
 // chunk and 4-byte scale quad (moe_mxfp4.hip's A-operand loads), widens two of the four code words per 64-deep stage with
 // v_cvt_scalef32_pk_bf16_fp4 and writes the two k-tiles lane-linear (ds_write_b128) into the LDS slots the bf16 kernel's DMA fills.
 // A unit is two stages: words 0, 1 then words 2, 3 of the codes in registers; the next unit's codes are loaded into the same registers
 // right after the second half is written, ahead of that stage's MFMAs.  Everything else -- work unit, grid, prefix sum, token gather,
 // MFMA loop, epilogues, clamps -- is the code below, once.
+//
+// FMT = MT_FP8B is the kernel over block-scaled FP8 expert tables (include/ssd_hip_moe_tiled_fp8b.h): "fp8 frag" codes and one fp32
+// scale per (16-row group, 128-column block).  One 1 KiB code tile is 16 rows x 64 columns, exactly one stage of one row group, so the
+// weight stage is ONE 16-byte load per lane and row group: fp8x8_to_bf16 (exact, scale operand 1.0) widens words 0, 1 into the stage's
+// first k-tile and words 2, 3 into its second, one lane-linear ds_write_b128 each into the slots the bf16 DMA fills.  The scale cannot
+// be folded into a bf16 weight, so it multiplies a partial sum: per stage and token tile the wave's NTW tiles go through a zeroed fp32
+// temporary (two k-tiles), then acc = fma(s, temporary, acc).  The token tile is the outer loop of a stage and the k-tile the inner
+// one, so only NTW temporaries are live per token tile; there are two sets, and the fmas of token tile mt are issued behind the
+// MFMAs of mt + 1.  The four scales of a wave's row groups are wave-uniform and are read through the scalar cache one block ahead.
 #include "common.h"
 #include "mx4.h"
+#include "gemm_fp8.h"
 #include "ssd_hip_moe_tiled.h"
 #include "ssd_hip_moe_tiled_mxfp4.h"
+#include "ssd_hip_moe_tiled_fp8b.h"
 
 typedef __attribute__((address_space(1))) void* mt_gptr_t;
 typedef __attribute__((address_space(3))) void* mt_lptr_t;
 
+// the table format of an instantiation
+enum { MT_BF16 = 0, MT_MX4 = 1, MT_FP8B = 2 };
+
 // grid (nb * spans): workgroup id -> (span, block b of the bound nb = T k / BM + E), blocks fastest.  WM x WN waves; wave (wm, wn)
 // owns the span's row groups wn NTW .. + NTW and the block's token tiles wm, wm + WM, ... (dealt round-robin, so a ragged block's
 // tiles spread over the wm).
-// Wf: the bf16 fragment tables, or (MX4) the code tables with their scale quads in Sf.
-template <int EPI, int BM, int BN, int WM, int WN, bool MX4>
+// Wf: the bf16 fragment tables, or the code tables with their scales in Sf (MT_MX4: e8m0 scale quads; MT_FP8B: fp32 per group and block).
+template <int EPI, int BM, int BN, int WM, int WN, int FMT>
 __global__ void __launch_bounds__(64 * WM * WN, WM * WN <= 4 ? 2 : 1)
 moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, const uint32_t* __restrict__ Sf,
                  const int32_t* __restrict__ offs, const int32_t* __restrict__ perm, bf16_t* __restrict__ out, int T, int k, int E, int N,
                  int K, int nb) {
+  constexpr bool MX4 = FMT == MT_MX4, F8B = FMT == MT_FP8B;
   constexpr int NW = WM * WN;
   constexpr int TW = BN / 16, TX = BM / 16, TT = TW + TX;      // fragment tiles per k-tile: table groups first, then token tiles
   constexpr int GW = TW / NW, GX = TX / NW;                    // tiles of each kind a wave stages per k-tile
@@ -94,6 +109,8 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
     if constexpr (MX4) {                                       // a unit of 4 k-tiles is one code chunk and one scale quad per lane
       wsrc[i] = Wf + ((((size_t)e * NG + grp) * (KT >> 2)) << 6) + lane;
       ssrc[i] = Sf + ((((size_t)e * NG + grp) * (KT >> 2)) << 4) + (lane & 15);
+    } else if constexpr (F8B) {                                // a stage of 2 k-tiles is one code chunk per lane
+      wsrc[i] = Wf + ((((size_t)e * NG + grp) * (KT >> 1)) << 6) + lane;
     } else {
       wsrc[i] = Wf + ((((size_t)e * NG + grp) * KT) << 6) + lane;
     }
@@ -124,7 +141,7 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
 #pragma unroll
     for (int i = 0; i < GW; ++i) {
       qc[i] = __builtin_nontemporal_load(wsrc[i] + ((size_t)c << 6));
-      sc[i] = __builtin_nontemporal_load(ssrc[i] + ((size_t)c << 4));
+      if constexpr (MX4) sc[i] = __builtin_nontemporal_load(ssrc[i] + ((size_t)c << 4));
     }
   };
   auto widen = [&](auto half, int buf) {
@@ -134,12 +151,30 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) lds[buf][ks][wave * GW + i][lane] = mx4_to_bf16(qc[i][2 * HALF + ks], mx4_scale(sc[i], 2 * HALF + ks));
   };
+  // FP8B: load_q(kb) takes the codes of STAGE kb, and one widening fills both k-tiles of a stage
+  auto widen8 = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < GW; ++i)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) lds[buf][ks][wave * GW + i][lane] = fp8x8_to_bf16(qc[i][2 * ks], qc[i][2 * ks + 1]);
+  };
+  // FP8B: the scales of this wave's NTW row groups, wave-uniform (e, span and wave come through readfirstlane / blockIdx): block c in
+  // sv, block c + 1 already requested in sn.  Groups past the table read the clamped group's scale and are never stored
+  const float* sp[NTW];
+  float sv[NTW], sn[NTW];
+  if constexpr (F8B) {
+#pragma unroll
+    for (int nt = 0; nt < NTW; ++nt) {
+      sp[nt] = reinterpret_cast<const float*>(Sf) + ((size_t)e * NG + min(g0 + wn * NTW + nt, NG - 1)) * (KT >> 2);
+      sn[nt] = sp[nt][0];
+    }
+  }
   auto issue = [&](int kb, int buf) {                          // the DMA of stage kb
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const int kt = 2 * kb + ks;
       if (kt < KT) {
-        if constexpr (!MX4) stage_w(kt, buf, ks);
+        if constexpr (FMT == MT_BF16) stage_w(kt, buf, ks);
         stage_x(kt, buf, ks);
       }
     }
@@ -152,18 +187,72 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
     for (int mt = 0; mt < MTW; ++mt) acc[nt][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int nkb = (KT + 1) >> 1;
-  if constexpr (MX4) load_q(0);
+  if constexpr (MX4 || F8B) load_q(0);
   issue(0, 0);
   if constexpr (MX4) widen(std::integral_constant<int, 0>{}, 0);
+  if constexpr (F8B) {
+    widen8(0);
+    if (1 < nkb) load_q(1);
+  }
   for (int kb = 0; kb < nkb; ++kb) {
     const int cur = kb & 1;
     // RAW: this wave's DMA of stage kb has landed, and after the barrier every wave's has.  WAR: every wave finished reading buffer
     // cur ^ 1 (stage kb - 1) before the barrier, so it may be restaged right after it.  MX4: lgkmcnt(0) is the same RAW for the widened
-    // tiles' ds_writes, and vmcnt(0) also lands the next unit's codes in their registers.
+    // tiles' ds_writes, and vmcnt(0) also lands the next unit's codes in their registers (FP8B: the next stage's codes, and lgkmcnt(0)
+    // the next block's scales).
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+    if constexpr (F8B) {
+      // the vmcnt(0) above landed the code registers, but the compiler counts for itself: let it see them used HERE, with nothing in
+      // flight, so that the widening below does not wait for the token DMA issued in between
+#pragma unroll
+      for (int i = 0; i < GW; ++i) asm volatile("" : "+v"(qc[i]));
+    }
     if (kb + 1 < nkb) issue(kb + 1, cur ^ 1);
+    if constexpr (F8B) {
+      // K % 128 == 0: a stage is half a block, never ragged.  Even stages open a block: its scales, and the request for the next one's
+      if (!(kb & 1)) {
+        const int cn = min((kb >> 1) + 1, (KT >> 2) - 1);
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) {
+          sv[nt] = sn[nt];
+          sn[nt] = sp[nt][cn];
+        }
+      }
+      u32x4_t a[2][NTW];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) a[ks][nt] = lds[cur][ks][wn * NTW + nt][lane];
+      f32x4_t tmp[2][NTW];                                       // the stage's own sums of token tiles mt (even) and mt (odd)
+#pragma unroll
+      for (int mt = 0; mt <= MTW; ++mt) {
+        if (mt < MTW && mt < mtv) {
+          const int xt = TW + wm + WM * min(mt, MTW - 1);
+          const u32x4_t b0 = lds[cur][0][xt][lane], b1 = lds[cur][1][xt][lane];
+#pragma unroll
+          for (int nt = 0; nt < NTW; ++nt) tmp[mt & 1][nt] = mfma16(a[0][nt], b0, f32x4_t{0.f, 0.f, 0.f, 0.f});   // from +0
+#pragma unroll
+          for (int nt = 0; nt < NTW; ++nt) tmp[mt & 1][nt] = mfma16(a[1][nt], b1, tmp[mt & 1][nt]);
+        }
+        // behind the first token tile's MFMAs, which run on while the VALU widens: stage kb + 1 from the codes the vmcnt(0) above
+        // landed; once they are written the registers take stage kb + 2's
+        if (mt == 0 && kb + 1 < nkb) {
+          widen8(cur ^ 1);
+          if (kb + 2 < nkb) load_q(kb + 2);
+        }
+        // the previous token tile's fmas, under this one's MFMAs
+        if (mt >= 1 && mt - 1 < mtv) {
+#pragma unroll
+          for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4)
+              acc[nt][mt - 1][r4] = __builtin_fmaf(sv[nt], tmp[(mt - 1) & 1][nt][r4], acc[nt][mt - 1][r4]);
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       if (2 * kb + ks >= KT) continue;                         // an odd K / 32: the last stage holds one k-tile
@@ -232,45 +321,52 @@ moe_tiled_kernel(const bf16_t* __restrict__ X, const u32x4_t* __restrict__ Wf, c
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-template <int EPI, int BM, int BN, int WM, int WN, bool MX4>
+template <int EPI, int BM, int BN, int WM, int WN, int FMT>
 static int tiled_go(const void* rows_in, const void* w_frag, const void* s_frag, const int32_t* offs, const int32_t* perm, void* out, int T,
                     int k, int E, int N, int K, hipStream_t st) {
   // sum_e ceil(n_e / BM) <= floor(T k / BM) + E: a grid that depends on no device data
   const long nb = (long)T * k / BM + E, spans = (N + BN - 1) / BN;
   if (nb * spans > 0x7fffffffL) return SSD_ERR_SHAPE;
-  hipLaunchKernelGGL((moe_tiled_kernel<EPI, BM, BN, WM, WN, MX4>), dim3((unsigned)(nb * spans)), dim3(64 * WM * WN), 0, st,
+  hipLaunchKernelGGL((moe_tiled_kernel<EPI, BM, BN, WM, WN, FMT>), dim3((unsigned)(nb * spans)), dim3(64 * WM * WN), 0, st,
                      (const bf16_t*)rows_in, (const u32x4_t*)w_frag, (const uint32_t*)s_frag, offs, perm, (bf16_t*)out, T, k, E, N, K,
                      (int)nb);
   return hipGetLastError() == hipSuccess ? SSD_OK : SSD_ERR_LAUNCH;
 }
 
-// both entries' checks and launch; s_frag is null for bf16 tables
-template <bool MX4>
+// every entry's checks and launch; s_frag is null for bf16 tables
+template <int FMT>
 static int tiled_entry(const void* rows_in, const void* w_frag, const void* s_frag, const int32_t* offs, const int32_t* perm, void* out,
                        int T, int k, int E, int N, int K, int epilogue, void* stream) {
-  if (!rows_in || !w_frag || (MX4 && !s_frag) || !offs || !perm || !out) return SSD_ERR_ARG;
+  if (!rows_in || !w_frag || (FMT != MT_BF16 && !s_frag) || !offs || !perm || !out) return SSD_ERR_ARG;
   if (epilogue != SSD_MOE_EPI_UP && epilogue != SSD_MOE_EPI_DOWN) return SSD_ERR_ARG;
   if (T <= 0 || k < 1 || k > SSD_MOE_MAX_K || E < SSD_MOE_MIN_E || E > SSD_MOE_MAX_E || (E & 7) || k > E) return SSD_ERR_SHAPE;
   if ((long)T * k > (1L << 24)) return SSD_ERR_SHAPE;
-  if (K <= 0 || (K & (MX4 ? 127 : 31)) || N <= 0) return SSD_ERR_SHAPE;
+  if (K <= 0 || (K & (FMT != MT_BF16 ? 127 : 31)) || N <= 0) return SSD_ERR_SHAPE;
   if (epilogue == SSD_MOE_EPI_UP ? (N & 63) : (N & 15)) return SSD_ERR_SHAPE;
   // 128 entries x 128 table rows, 2 x 2 waves (64 KiB LDS: two workgroups per CU).  A 256 x 128 form with 4 x 2 waves was measured
   // and lost at every T (DESIGN.md "Tiled expert GEMM"): an expert's ragged last block leaves more of a larger workgroup idle
   // The mx4 form keeps that shape and the 64-deep stage: a unit is widened in two halves from codes held in registers, so LDS stays
   // 64 KiB and two workgroups share a CU (DESIGN.md "Tiled expert GEMM over MXFP4 tables")
+  // The fp8b form keeps them too: one 16-byte code load per lane and row group is one stage (DESIGN.md "Tiled expert GEMM over
+  // block-scaled FP8 tables")
   if (epilogue == SSD_MOE_EPI_UP)
-    return tiled_go<SSD_MOE_EPI_UP, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2, MX4>(rows_in, w_frag, s_frag, offs, perm, out, T, k, E, N, K,
+    return tiled_go<SSD_MOE_EPI_UP, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2, FMT>(rows_in, w_frag, s_frag, offs, perm, out, T, k, E, N, K,
                                                                                    (hipStream_t)stream);
-  return tiled_go<SSD_MOE_EPI_DOWN, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2, MX4>(rows_in, w_frag, s_frag, offs, perm, out, T, k, E, N, K,
+  return tiled_go<SSD_MOE_EPI_DOWN, SSD_MOE_TILED_BM, SSD_MOE_TILED_BN, 2, 2, FMT>(rows_in, w_frag, s_frag, offs, perm, out, T, k, E, N, K,
                                                                                    (hipStream_t)stream);
 }
 
 extern "C" int ssd_moe_gemm_tiled(const void* rows_in, const void* w_frag, const int32_t* offs, const int32_t* perm, void* out, int T,
                                   int k, int E, int N, int K, int epilogue, void* stream) {
-  return tiled_entry<false>(rows_in, w_frag, nullptr, offs, perm, out, T, k, E, N, K, epilogue, stream);
+  return tiled_entry<MT_BF16>(rows_in, w_frag, nullptr, offs, perm, out, T, k, E, N, K, epilogue, stream);
 }
 
 extern "C" int ssd_moe_gemm_tiled_mxfp4(const void* rows_in, const void* q_frag, const void* s_frag, const int32_t* offs,
                                         const int32_t* perm, void* out, int T, int k, int E, int N, int K, int epilogue, void* stream) {
-  return tiled_entry<true>(rows_in, q_frag, s_frag, offs, perm, out, T, k, E, N, K, epilogue, stream);
+  return tiled_entry<MT_MX4>(rows_in, q_frag, s_frag, offs, perm, out, T, k, E, N, K, epilogue, stream);
+}
+
+extern "C" int ssd_moe_gemm_tiled_fp8b(const void* rows_in, const void* q_frag, const float* s_grp, const int32_t* offs,
+                                       const int32_t* perm, void* out, int T, int k, int E, int N, int K, int epilogue, void* stream) {
+  return tiled_entry<MT_FP8B>(rows_in, q_frag, s_grp, offs, perm, out, T, k, E, N, K, epilogue, stream);
 }

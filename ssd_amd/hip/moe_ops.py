@@ -1,5 +1,5 @@
 """ctypes table and torch front end of the mixture-of-experts entry points (include/ssd_hip_moe.h, include/ssd_hip_moe_mxfp4.h,
-include/ssd_hip_moe_fp8b.h, include/ssd_hip_moe_tiled.h, include/ssd_hip_moe_tiled_mxfp4.h).
+include/ssd_hip_moe_fp8b.h, include/ssd_hip_moe_tiled.h, include/ssd_hip_moe_tiled_mxfp4.h, include/ssd_hip_moe_tiled_fp8b.h).
 
 Kept apart from ``lib.SIGNATURES`` and the other additive tables: these bind on the same libssdhip.so.  As in ops.py, nothing here
 computes in torch; the calls enqueue on the current stream and are hipGraph-capturable.  The expert tables are laid out by
@@ -47,6 +47,11 @@ MOE_TILED_MX4_SIGNATURES = {
     "ssd_moe_gemm_tiled_mxfp4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
 }
 
+# name -> argtypes, exactly include/ssd_hip_moe_tiled_fp8b.h
+MOE_TILED_FP8B_SIGNATURES = {
+    "ssd_moe_gemm_tiled_fp8b": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+}
+
 
 def load_moe_library():
     return bind(MOE_SIGNATURES)
@@ -66,6 +71,10 @@ def load_moe_tiled_library():
 
 def load_moe_tiled_mx4_library():
     return bind(MOE_TILED_MX4_SIGNATURES)
+
+
+def load_moe_tiled_fp8b_library():
+    return bind(MOE_TILED_FP8B_SIGNATURES)
 
 
 def moe_route(logits, ld: int, T: int, E: int, k: int, norm: bool, topk_ids, topk_w, offs, perm):
@@ -103,6 +112,12 @@ def moe_gemm_fp8b(rows_in, q_frag, s_grp, offs, perm, out, T: int, k: int, E: in
     """moe_gemm over E block-scaled FP8 tables [N][K]: q_frag E * N * K bytes of fp8 frag codes, s_grp fp32 [E][N / 16][K / 128]."""
     _check(load_moe_fp8b_library().ssd_moe_gemm_fp8b(_p(rows_in), _p(q_frag), _p(s_grp), _p(offs), _p(perm), _p(out), T, k, E, N, K,
                                                      epilogue, _stream()), "ssd_moe_gemm_fp8b")
+
+
+def moe_gemm_tiled_fp8b(rows_in, q_frag, s_grp, offs, perm, out, T: int, k: int, E: int, N: int, K: int, epilogue: int):
+    """moe_gemm_fp8b on the compute-bound LDS-tiled kernel (long prefills): the same arguments and tables."""
+    _check(load_moe_tiled_fp8b_library().ssd_moe_gemm_tiled_fp8b(_p(rows_in), _p(q_frag), _p(s_grp), _p(offs), _p(perm), _p(out), T, k, E, N,
+                                                                 K, epilogue, _stream()), "ssd_moe_gemm_tiled_fp8b")
 
 
 def moe_combine(d_rows, topk_w, h_rows, T: int, k: int, H: int):

@@ -394,6 +394,8 @@ class HipDecoder:
             MOE.moe_gemm_tiled_mxfp4(rows_in, self.w[name], self.w[name + "_scale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
         elif self.mx4:
             MOE.moe_gemm_mxfp4(rows_in, self.w[name], self.w[name + "_scale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
+        elif self.fp8 and T >= self.MOE_TILED_FP8B_MIN_T:
+            MOE.moe_gemm_tiled_fp8b(rows_in, self.w[name], self.w[name + "_bscale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
         elif self.fp8:
             MOE.moe_gemm_fp8b(rows_in, self.w[name], self.w[name + "_bscale"], self.moe_offs, self.moe_perm, out, T, k, E, N, K, epi)
         elif T >= self.MOE_TILED_MIN_T:
@@ -689,6 +691,10 @@ class HipDecoder:
     # mxfp4 expert GEMMs of at least this many rows run on the tiled kernel's mxfp4 form (ssd_moe_gemm_tiled_mxfp4); shorter forwards
     # stay on the weight-streaming one (csrc/moe_mxfp4.hip).  Measured: the table in DESIGN.md "Tiled expert GEMM over MXFP4 tables"
     MOE_TILED_MX4_MIN_T = 1024
+    # block-scaled fp8 expert GEMMs of at least this many rows run on the tiled kernel's fp8b form (ssd_moe_gemm_tiled_fp8b); shorter
+    # forwards stay on the weight-streaming one (csrc/moe_fp8b.hip).  Measured: the table in DESIGN.md "Tiled expert GEMM over
+    # block-scaled FP8 tables"
+    MOE_TILED_FP8B_MIN_T = 1024
     # mxfp4 linears of up to this many rows run on the mxfp4 GEMM itself; longer prompts dequantize into self._deq first
     MX4_DIRECT_MAX_T = 128
 
