@@ -25,6 +25,7 @@ from ssd_amd.hip import quant_ops as Q
 from ssd_amd.hip import fp8b_ops as F8B
 from ssd_amd.hip import w4_ops as W4
 from ssd_amd.hip import w4zp_ops as W4Z
+from ssd_amd.hip import w8_ops as W8
 from ssd_amd.hip import mx4_ops as MX4
 from ssd_amd.hip import kv8_ops as KV8
 from ssd_amd.hip import swa_ops as SWA
@@ -78,6 +79,8 @@ def make_cos_sin(head_dim: int, max_pos: int, theta: float, device) -> torch.Ten
 
 
 class HipDecoder:
+    w8 = False      # quantization="w8a16" (set per instance in __init__; a decoder of another kind is not one)
+
     def __init__(self, cfg: ModelConfig, *, max_tokens: int, max_seqs: int, max_blocks: int, block_size: int,
                  max_model_len: int, device: torch.device, tp_rank: int = 0, tp_size: int = 1, tp_group=None,
                  max_logit_rows: int | None = None, max_split_tokens: int = 256, force_collectives: bool = False,
@@ -116,18 +119,19 @@ class HipDecoder:
         if self.kv8 and cfg.head_dim not in (64, 128):
             raise ValueError(f"kv_cache_dtype='fp8' needs head_dim 64 or 128, got {cfg.head_dim}")
         assert not self.kv8 or (tp_size == 1 and not force_collectives and taps is None), "fp8 KV caches are single-rank, without taps"
-        # quantization="fp8" | "w4a16" | "mxfp4": the decoder linears are codes + side tables in the format's device form (the formats
+        # quantization="fp8" | "w4a16" | "w8a16" | "mxfp4": the decoder linears are codes + side tables in the format's device form (the formats
         # and their host forms: ssd_amd/quant.py; load_weights) and run on that format's GEMM (_gemm).  Every bf16-only fused form
         # (norm prologues, the QKV+RoPE epilogue, split-K slabs, attention + o_proj, the resident chain / tree segments, prefill
         # partials) is off, so a layer is norm -> GEMM -> RoPE / KV store -> attention -> GEMM -> norm -> GEMM -> GEMM.  Which GEMM a
         # linear runs on follows from the tables it has, so per-row and block-scaled fp8 linears, and symmetric and zero-point int4
         # ones (w4_zero_point=True: the on-load quantizer makes the latter), mix freely in one model.  Single rank only (Config
         # refuses the rest).
-        assert quantization in (None, "fp8", "w4a16", "mxfp4"), quantization
+        assert quantization in (None, "fp8", "w4a16", "w8a16", "mxfp4"), quantization
         self.fp8 = quantization == "fp8"
         self.w4 = quantization == "w4a16"
+        self.w8 = quantization == "w8a16"
         self.mx4 = quantization == "mxfp4"
-        self.quantized = self.fp8 or self.w4 or self.mx4
+        self.quantized = self.fp8 or self.w4 or self.w8 or self.mx4
         if w4_zero_point and not self.w4:
             raise ValueError(f"w4_zero_point=True needs quantization='w4a16', got {quantization!r}")
         self.w4_zero_point = w4_zero_point
@@ -150,6 +154,9 @@ class HipDecoder:
         if self.w4 and any(k % quant.W4_GROUP for k in (self.h, self.qn, self.I)):
             raise ValueError(f"quantization='w4a16' needs hidden_size, num_heads * head_dim and intermediate_size to be multiples of "
                              f"{quant.W4_GROUP} (the group size), got {self.h}, {self.qn}, {self.I}")
+        if self.w8 and any(k % quant.W8_GROUP for k in (self.h, self.qn, self.I)):
+            raise ValueError(f"quantization='w8a16' needs hidden_size, num_heads * head_dim and intermediate_size to be multiples of "
+                             f"{quant.W8_GROUP} (the group size), got {self.h}, {self.qn}, {self.I}")
         if self.mx4 and any(k % quant.MX4_GROUP for k in (self.h, self.qn, self.I)):
             raise ValueError(f"quantization='mxfp4' needs hidden_size, num_heads * head_dim and intermediate_size to be multiples of "
                              f"{quant.MX4_GROUP} (four 32-column blocks: one device unit), got {self.h}, {self.qn}, {self.I}")
@@ -273,8 +280,9 @@ class HipDecoder:
         # the bf16 prefill GEMMs (compute-bound there, so the halved weight bytes buy nothing).  Allocated once: prefill hipGraphs
         # bake its pointer.
         # The same scratch serves w4a16 prompts longer than W4_DIRECT_MAX_T rows.
-        # ... and mxfp4 prompts longer than MX4_DIRECT_MAX_T rows.
-        direct_max = self.W4_DIRECT_MAX_T if self.w4 else self.MX4_DIRECT_MAX_T if self.mx4 else self.FP8_DIRECT_MAX_T
+        # ... and mxfp4 prompts longer than MX4_DIRECT_MAX_T rows, and w8a16 prompts longer than W8_DIRECT_MAX_T rows.
+        direct_max = (self.W4_DIRECT_MAX_T if self.w4 else self.W8_DIRECT_MAX_T if self.w8 else self.MX4_DIRECT_MAX_T if self.mx4
+                      else self.FP8_DIRECT_MAX_T)
         deq_shapes = pf_shapes[:2] if self.moe else pf_shapes[:4]       # a MoE target's experts are never dequantized: q | k | v and o only
         self._deq = (z(max(n * k for n, k in deq_shapes)) if self.quantized and max_tokens > direct_max else None)
         st = min(T, max_split_tokens)
@@ -533,7 +541,7 @@ class HipDecoder:
 
     def _kind(self) -> str | None:
         """The `quantization` value this decoder runs, read off its flags."""
-        return "fp8" if self.fp8 else "w4a16" if self.w4 else "mxfp4" if self.mx4 else None
+        return "fp8" if self.fp8 else "w4a16" if self.w4 else "w8a16" if self.w8 else "mxfp4" if self.mx4 else None
 
     def _quantize_on_load(self, w: torch.Tensor):
         """The host form this decoder's own quantizer gives a bf16 linear."""
@@ -541,6 +549,8 @@ class HipDecoder:
             return quant.quantize_fp8(w)
         if self.mx4:
             return quant.quantize_mxfp4(w)
+        if self.w8:
+            return quant.quantize_w8a16(w)
         return quant.quantize_w4a16_zp(w) if self.w4_zero_point else quant.quantize_w4a16(w)
 
     def _load_quantized(self, name: str, w) -> None:
@@ -552,7 +562,7 @@ class HipDecoder:
             row_map = quant.qkv_row_map(self.nh, self.nkv, self.hd).to(self.device)
         elif name.endswith("gate_up_proj.weight"):
             row_map = quant.gate_up_row_map(N).to(self.device)
-        load = self._load_fp8 if self.fp8 else self._load_mx4 if self.mx4 else self._load_w4
+        load = self._load_fp8 if self.fp8 else self._load_mx4 if self.mx4 else self._load_w8 if self.w8 else self._load_w4
         for suffix, t in load(name, w, N, K, row_map).items():
             self.w[name + suffix] = t
 
@@ -584,6 +594,14 @@ class HipDecoder:
             W4Z.w4zp_rows_to_frag(packed, s, zero, out[""], out["_scale"], out["_zero"], N, K, row_map=row_map)
         else:
             W4.w4_rows_to_frag(packed, s, out[""], out["_scale"], N, K, row_map=row_map)
+        return out
+
+    def _load_w8(self, name: str, w, N: int, K: int, row_map) -> dict:
+        """W8Tensor -> w8 frag codes + "_scale" bf16 frag scales (include/ssd_hip_w8a16.h)."""
+        codes, s = w.codes.contiguous(), w.scale.to(BF16).contiguous()
+        assert codes.dtype == torch.uint8 and tuple(s.shape) == (N, K // quant.W8_GROUP), (name, codes.dtype, s.shape)
+        out = {"": self._frag(N * K, torch.uint8), "_scale": self._frag(N * K // quant.W8_GROUP, BF16)}
+        W8.w8_rows_to_frag(codes, s, out[""], out["_scale"], N, K, row_map=row_map)
         return out
 
     def _load_mx4(self, name: str, w, N: int, K: int, row_map) -> dict:
@@ -685,6 +703,8 @@ class HipDecoder:
     FP8_DIRECT_MAX_T = 128
     # w4a16 linears of up to this many rows run on the w4a16 GEMM itself; longer prompts dequantize into self._deq first
     W4_DIRECT_MAX_T = 128
+    # w8a16 linears of up to this many rows run on the w8a16 GEMM itself; longer prompts dequantize into self._deq first
+    W8_DIRECT_MAX_T = 128
     # bf16 expert GEMMs of at least this many rows run on the compute-bound tiled kernel (csrc/moe_tiled.hip); shorter forwards stay
     # on the weight-streaming one (csrc/moe.hip).  Measured: the table in DESIGN.md "Tiled expert GEMM"
     MOE_TILED_MIN_T = 512
@@ -746,6 +766,8 @@ class HipDecoder:
             if zero is not None:
                 return W4Z.gemm_w4a16_zp, W4Z.w4zp_dequant_frag, self.W4_DIRECT_MAX_T, (scale, zero)
             return W4.gemm_w4a16, W4.w4_dequant_frag, self.W4_DIRECT_MAX_T, (scale,)
+        if self.w8:                     # w8a16 codes + group scales
+            return W8.gemm_w8a16, W8.w8_dequant_frag, self.W8_DIRECT_MAX_T, (scale,)
         if self.mx4:                    # mxfp4 codes + block scale bytes
             return MX4.gemm_mxfp4, MX4.mx4_dequant_frag, self.MX4_DIRECT_MAX_T, (scale,)
         return Q.gemm_fp8, Q.fp8_dequant_frag, self.FP8_DIRECT_MAX_T, (scale,)      # fp8 codes + row scales

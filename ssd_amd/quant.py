@@ -1,5 +1,5 @@
 """Weight-only quantization of the decoder linears: FP8 (OCP e4m3fn) with one scale per row, W[N, K] ~= s[n] * q[n, k], and W4A16
-(int4 with one scale per row and 128-column group, further down), and MXFP4 (e2m1 codes with one e8m0 scale per row and 32-column
+(int4 with one scale per row and 128-column group, further down), W8A16 (int8, the same groups), and MXFP4 (e2m1 codes with one e8m0 scale per row and 32-column
 block, at the end).
 
 The one-time load math is torch on the device; the re-tiling into the kernel layout is csrc/gemm_fp8.hip (ssd_fp8_rows_to_frag) and
@@ -25,8 +25,8 @@ def is_quantized_linear(name: str) -> bool:
     return name.startswith("model.layers.") and name.endswith(LINEAR_SUFFIXES)
 
 
-# Host forms.  A pre-quantized decoder linear travels from a checkpoint (or a host quantizer) to the decoder as one of five
-# NamedTuples: FP8Tensor, FP8BTensor, W4Tensor, W4ZTensor, MX4Tensor.  Each answers, here and nowhere else: `native`, the
+# Host forms.  A pre-quantized decoder linear travels from a checkpoint (or a host quantizer) to the decoder as one of six
+# NamedTuples: FP8Tensor, FP8BTensor, W4Tensor, W4ZTensor, W8Tensor, MX4Tensor.  Each answers, here and nowhere else: `native`, the
 # `quantization` value of the target that runs it as it is; `phrase`, what refusals call it; shape(), the logical (N, K); and
 # dequantize(), the bf16 matrix such a target computes with (what a bf16 target loads instead).  Every field of every type has one
 # row per output row, so packing q | k | v or gate | up (cat_rows) and moving (to_device) are generic.
@@ -297,6 +297,52 @@ def w4z_as_symmetric(w: W4ZTensor) -> "W4Tensor | W4ZTensor":
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# W8A16 (include/ssd_hip_w8a16.h): signed int8 codes q in [-128, 127] with one bf16 scale per output row and 128-column group,
+# W = s[n, k // 128] * q[n, k] (csrc/gemm_w8a16.hip).  Symmetric, round to nearest, fp32 on the tensor's device:
+#
+#     amax = max |w| over the group
+#     s = bf16_rne(amax / 127)                        (an all-zero group gets s = 1, q = 0)
+#     q = clamp(rne(w / float(s)), -128, 127)
+#
+# The host form is the row form of the header: codes uint8 [N, K], the byte of column k is u = q + 128 (compressed-tensors
+# "pack-quantized" int32 [N, K / 4] words viewed as bytes); scales bf16 [N, K / 128].  A per-channel checkpoint repeats its scale.
+# ---------------------------------------------------------------------------------------------------------------------
+W8_GROUP = 128
+
+
+class W8Tensor(NamedTuple):
+    """A W8A16 decoder linear in the host row form: codes uint8 [N, K] (u = q + 128), scale bf16 [N, K / 128]."""
+    codes: torch.Tensor
+    scale: torch.Tensor
+    native, phrase = "w8a16", "int8 (w8a16)"
+
+    def shape(self) -> tuple[int, int]:
+        return tuple(self.codes.shape)
+
+    def dequantize(self) -> torch.Tensor:
+        return dequantize_w8a16(*self)
+
+
+def quantize_w8a16(w: torch.Tensor) -> W8Tensor:
+    """[N, K] bf16 (K % 128 == 0) -> W8Tensor(codes uint8 [N, K], scale bf16 [N, K / 128]), on w's device."""
+    N, K = w.shape
+    assert K % W8_GROUP == 0, f"W8A16 needs K % {W8_GROUP} == 0, got {K}"
+    wf = w.float().reshape(N, K // W8_GROUP, W8_GROUP)
+    s = (wf.abs().amax(-1) / 127.0).to(torch.bfloat16)
+    s = torch.where(s == 0, torch.ones_like(s), s)
+    q = torch.round(wf / s.float()[..., None]).clamp(-128, 127).reshape(N, K)
+    return W8Tensor((q + 128).to(torch.uint8), s)
+
+
+def dequantize_w8a16(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16(s * q), the product in fp32: the weights a W8A16 target computes with, as a bf16 matrix (oracles, a bf16 decoder given
+    int8 tensors)."""
+    q = codes.float() - 128.0
+    s = scale.float().repeat_interleave(W8_GROUP, dim=1)
+    return (q * s).to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # MXFP4 (OCP microscaling FP4): e2m1 codes (4 bits s e e m: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 for codes 0..7, sign in bit 3) with
 # one e8m0 scale byte b per output row and block of 32 consecutive columns, W = 2^(b - 127) * e2m1(q) (csrc/gemm_mxfp4.hip).
 # Supported scale bytes are 2 <= b <= 252: there 0.5 * 2^(b - 127) is a normal bf16 number and 6 * 2^(b - 127) is finite, so every
@@ -383,11 +429,11 @@ def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# What the loaders and the decoder ask of a host form without knowing which of the five it is.
+# What the loaders and the decoder ask of a host form without knowing which of the six it is.
 # ---------------------------------------------------------------------------------------------------------------------
 def is_prequantized(w) -> bool:
     """Whether w is a pre-quantized decoder linear in one of the host forms (anything else is a plain tensor)."""
-    return isinstance(w, (FP8Tensor, FP8BTensor, W4Tensor, W4ZTensor, MX4Tensor))
+    return isinstance(w, (FP8Tensor, FP8BTensor, W4Tensor, W4ZTensor, W8Tensor, MX4Tensor))
 
 
 def cat_rows(parts: list):

@@ -470,7 +470,8 @@ def fp8_block_scheme(qc: dict | None) -> bool:
 def checkpoint_quantization(model_dir: str) -> str | None:
     """"fp8" for a compressed-tensors checkpoint with float 8-bit weights and per-channel or per-tensor scales and for a block-scaled
     fp8 one (fp8_block_scheme), "w4a16" for a pack-quantized one with symmetric int4 weights in groups of 128 columns and for an
-    AutoAWQ / GPTQ one (int4_checkpoint_scheme), "mxfp4" for an MXFP4 one (config.json quantization_config), None for an
+    AutoAWQ / GPTQ one (int4_checkpoint_scheme), "w8a16" for a pack-quantized one with symmetric int8 weights and per-channel or group-128 scales, "mxfp4" for an MXFP4 one
+    (config.json quantization_config), None for an
     unquantized one; every other quantization format is refused here, before any tensor is read."""
     return _checkpoint_kind(_quantization_config(model_dir))
 
@@ -501,10 +502,13 @@ def _checkpoint_kind(qc: dict | None) -> str | None:
         if wq.get("type") == "float" and wq.get("num_bits") == 4:
             kinds.add(_mxfp4_scheme(gname, wq, qc.get("format")))
             continue
+        if wq.get("type") == "int" and wq.get("num_bits") == 8:
+            kinds.add(_w8a16_scheme(gname, wq, g.get("input_activations"), qc.get("format")))
+            continue
         if wq.get("type") != "float" or wq.get("num_bits") != 8 or wq.get("strategy") not in ("channel", "tensor"):
             raise ValueError(f"unsupported compressed-tensors weight scheme in {gname}: {wq} (supported: type float, num_bits 8, "
-                             "strategy channel or tensor; or type int, num_bits 4, strategy group, group_size 128; or type float, num_bits 4, "
-                             "strategy group, group_size 32)")
+                             "strategy channel or tensor; or type int, num_bits 4, strategy group, group_size 128; or type int, num_bits 8, "
+                             "strategy channel or group with group_size 128; or type float, num_bits 4, strategy group, group_size 32)")
         kinds.add("fp8")
     if len(kinds) > 1:
         raise ValueError(f"compressed-tensors checkpoint mixes weight schemes {sorted(kinds)}")
@@ -550,6 +554,33 @@ def _w4a16_scheme(gname: str, wq: dict, fmt) -> str:
     if wq.get("actorder") not in (None, False, "static"):
         raise ValueError(f"int4 weights with actorder {wq.get('actorder')!r} in {gname} are not supported (no g_idx reordering)")
     return "w4a16"
+
+
+# compressed-tensors names of a W8A16 checkpoint, kept in one place.  The tensor suffixes and the packing (four 8-bit fields per
+# little-endian int32 word, field i = column 4j + i as the unsigned byte q + 128) are pack-quantized's own, the ones the int4
+# loader reads with eight 4-bit fields; that an 8-bit export uses them unchanged, and the "int-quantized" format name of W8A8
+# exports, are written from memory of the format and have not been checked against a published checkpoint (README, "W8A16").
+W8_FORMAT, W8A8_FORMAT = "pack-quantized", "int-quantized"
+W8_PACKED_SUFFIX, W8_SCALE_SUFFIX = ".weight_packed", ".weight_scale"
+
+
+def _w8a16_scheme(gname: str, wq: dict, acts, fmt) -> str:
+    """The int8 scheme a W8A16 target runs: symmetric, one scale per row (strategy channel) or per row and 128-column group, no
+    activation reordering, bf16 activations, pack-quantized."""
+    if fmt == W8A8_FORMAT or (acts or {}).get("num_bits") is not None:
+        raise ValueError(f"int8 activations (W8A8) in {gname} are not supported: type int, num_bits 8 weights load weight-only (W8A16) "
+                         f"alone, got format {fmt!r} and input_activations {acts!r}")
+    if fmt != W8_FORMAT:
+        raise ValueError(f"unsupported compressed-tensors format {fmt!r} for int8 weights in {gname}: only {W8_FORMAT}")
+    if wq.get("symmetric") is not True:
+        raise ValueError(f"asymmetric int8 weights (zero points) in {gname} are not supported: symmetric only")
+    if wq.get("strategy") not in ("channel", "group"):
+        raise ValueError(f"unsupported int8 weight strategy {wq.get('strategy')!r} in {gname}: only channel, or group with group_size 128")
+    if wq.get("strategy") == "group" and wq.get("group_size") != 128:
+        raise ValueError(f"unsupported int8 group_size {wq.get('group_size')!r} in {gname}: only 128")
+    if wq.get("actorder") not in (None, False, "static"):
+        raise ValueError(f"int8 weights with actorder {wq.get('actorder')!r} in {gname} are not supported (no g_idx reordering)")
+    return "w8a16"
 
 
 def _packed_sources(name: str) -> list[str] | None:
@@ -717,9 +748,9 @@ def _moe_experts(name: str, shape, index: dict, get, target: str | None = None):
 
 def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 1,
                      out_device: str | None = None, fp8: bool = False, w4a16: bool = False,
-                     mxfp4: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
+                     mxfp4: bool = False, w8a16: bool = False) -> Iterator[tuple[str, torch.Tensor]]:
     """Yields (name, bf16 tensor), and for a quantized decoder linear of a quantized checkpoint (checkpoint_quantization) one of
-    the host forms of ssd_amd/quant.py instead when the consumer is a target of that kind (``fp8`` / ``w4a16`` / ``mxfp4``: codes and
+    the host forms of ssd_amd/quant.py instead when the consumer is a target of that kind (``fp8`` / ``w4a16`` / ``mxfp4`` / ``w8a16``: codes and
     scales bit for bit, no re-quantization; _assemble has the rule); a bf16 consumer gets the exact dequantized bf16 matrix, sharded
     as usual, and a quantized target of another kind is refused before any tensor is read.  The forms, by checkpoint:
       * compressed-tensors fp8: quant.FP8Tensor(q float8_e4m3fn [N, K], s fp32 [N]); per-tensor scales of q / k / v and gate / up are
@@ -727,6 +758,8 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
       * block-scaled fp8 (fp8_block_scheme): quant.FP8BTensor(codes, rowscale fp32 [N, ceil(K / 128)]), every source tensor's
         weight_scale_inv expanded to one row of block scales per output row, then concatenated;
       * pack-quantized int4: quant.W4Tensor(packed int32 [N, K/8], scale bf16 [N, K/128]); fp16 / fp32 scales are rounded to bf16 once;
+      * pack-quantized int8 (_w8a16_scheme): quant.W8Tensor(codes uint8 [N, K], scale bf16 [N, K/128]); the int32 words are read as
+        their bytes, a per-channel scale [N, 1] is repeated across the groups, fp16 / fp32 scales are rounded to bf16 once;
       * AutoAWQ / GPTQ int4 (_load_awq_gptq): quant.W4ZTensor(packed, scale, zero), a plain W4Tensor when all its zero points are 8;
       * MXFP4: quant.MX4Tensor(packed uint8 [N, K/2], scale uint8 [N, K/32]); scale bytes outside 2..252 are refused.  A MoE layer's
         per-expert tensors become one MX4Tensor with a leading expert dimension (_moe_experts), and those of a block-scaled fp8
@@ -734,8 +767,9 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
     Unquantized tensors (e.g. the LM head) load as bf16."""
     from ssd_amd import quant
     from ssd_amd.quant import FP8, FP8Tensor, W4Tensor, MX4Tensor, check_mxfp4_scales, FP8_BLOCK, FP8BTensor, expand_fp8_block_scales
-    assert fp8 + w4a16 + mxfp4 <= 1
-    target = "fp8" if fp8 else "w4a16" if w4a16 else "mxfp4" if mxfp4 else None
+    from ssd_amd.quant import W8Tensor, W8_GROUP
+    assert fp8 + w4a16 + mxfp4 + w8a16 <= 1
+    target = "fp8" if fp8 else "w4a16" if w4a16 else "mxfp4" if mxfp4 else "w8a16" if w8a16 else None
     qc = _quantization_config(model_dir)
     kind = _checkpoint_kind(qc)
     scheme = int4_checkpoint_scheme(qc)
@@ -756,7 +790,7 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
             raise ValueError(f"{k}: float-4 weights with a global scale tensor (NVFP4) are not supported; only MXFP4")
     for k in index:
         if k.endswith("weight_zero_point"):
-            raise ValueError(f"{k}: asymmetric int4 weights (zero points) are not supported")
+            raise ValueError(f"{k}: asymmetric {'int8' if kind == 'w8a16' else 'int4'} weights (zero points) are not supported")
         if k.endswith("weight_g_idx"):
             raise ValueError(f"{k}: int4 weights with activation reordering (g_idx) are not supported")
 
@@ -777,6 +811,25 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
         if s.dtype not in (BF16, torch.float16, torch.float32):
             raise ValueError(f"{base}.weight_scale is {s.dtype}: expected bf16, fp16 or fp32")
         return W4Tensor(packed.contiguous(), s.to(BF16).contiguous())
+
+    def get_w8(name: str) -> W8Tensor:
+        base = name[:-len(".weight")]
+        packed, s = raw(base + W8_PACKED_SUFFIX), raw(base + W8_SCALE_SUFFIX)
+        N, KW = packed.shape
+        K = KW * 4
+        if packed.dtype != torch.int32:
+            raise ValueError(f"{base}{W8_PACKED_SUFFIX} is {packed.dtype}: expected int32 (four 8-bit fields per word)")
+        if base + ".weight_shape" in index:
+            shp = tuple(int(v) for v in raw(base + ".weight_shape").reshape(-1).tolist())
+            if shp != (N, K):
+                raise ValueError(f"{base}.weight_shape {shp} does not match weight_packed {tuple(packed.shape)} at 8 bits")
+        if K % W8_GROUP or tuple(s.shape) not in ((N, 1), (N, K // W8_GROUP)):
+            raise ValueError(f"{base}{W8_SCALE_SUFFIX} has shape {tuple(s.shape)}: expected [{N}, 1] (channel) or [{N}, {K // W8_GROUP}] "
+                             f"(group size {W8_GROUP}) for a [{N}, {K}] matrix")
+        if s.dtype not in (BF16, torch.float16, torch.float32):
+            raise ValueError(f"{base}{W8_SCALE_SUFFIX} is {s.dtype}: expected bf16, fp16 or fp32")
+        codes = packed.contiguous().view(torch.uint8)       # little-endian words: byte 4j + i of a row is field i of word j
+        return W8Tensor(codes, s.to(BF16).expand(N, K // W8_GROUP).contiguous())
 
     def get_mx4(name: str) -> MX4Tensor:
         base = name[:-len(".weight")]
@@ -810,7 +863,7 @@ def load_safetensors(cfg: ModelConfig, model_dir: str, rank: int = 0, tp: int = 
 
     def get(name: str):
         if name not in index and name.endswith(".weight") and name[:-len(".weight")] + ".weight_packed" in index:
-            return get_mx4(name) if kind == "mxfp4" else get_w4(name)
+            return get_mx4(name) if kind == "mxfp4" else get_w8(name) if kind == "w8a16" else get_w4(name)
         t = raw(name)
         if t.dtype == FP8:
             if not ckpt_fp8:
